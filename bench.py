@@ -1,8 +1,14 @@
 #!/usr/bin/env python
-"""Benchmark of the drone step path: env-steps/s per node, HBM roofline, CPU baseline.
+"""Benchmark of the drone step path: env-steps/s per node; with --full also the HBM roofline, the CPU
+baseline and every extra point.
 
-    python bench.py [--gpus N --steps K --warmup W]                      # 1 GPU
+    python bench.py [--gpus N --steps K --warmup W]                      # 1 GPU, the headline only
+    python bench.py --full [...]                                         # + everything else it measures
+    python bench.py --dump-outputs DIR [...]                             # + the last timed step's outputs as .npy
     python -m torch.distributed.run --nproc-per-node N bench.py --gpus N  # N GPUs
+
+A plain run sets up, warms up, times the K steps and prints the result line;
+the fields of the other measurements are null in it.
 
 A "step" is one frame of every drone on every rank: one ``dd_step`` launch
 per GPU over its resident shard (state, actions and outputs already in HBM).
@@ -63,7 +69,18 @@ def parse():
                         "1 with --dist-backend nccl: the N>1 code path on a one-GPU box)")
     p.add_argument("--hbm-point", type=int, default=16_777_216,
                    help="also time this many drones (HBM-resident) at N=1 and report it as hbm_point (0 = skip)")
-    return p.parse_args()
+    p.add_argument("--full", action="store_true",
+                   help="also measure everything beside the headline: the CPU baseline, the kernel-span roofline, "
+                        "hbm_point, rollout_point, the extra points and gather_point (each still has its own switch "
+                        "above); without it only the K timed steps run and those fields are null")
+    p.add_argument("--dump-outputs", default="", metavar="DIR",
+                   help="after the timed steps write what the last one returned (obs, reward, done) as DIR/<name>.npy")
+    args = p.parse_args()
+    if args.steps < 1:
+        p.error("--steps must be at least 1")
+    if args.gather_point and not args.full:
+        p.error("--gather-point is one of the --full measurements: pass --full with it")
+    return args
 
 
 # ----------------------------------------------------------------- CPU baseline
@@ -863,6 +880,38 @@ def socket_point(seed, dev, steps=2000):
             "reference_published": "300-500 steps/s (delivery_drone/SOCKET_API.md:373)"}
 
 
+DUMP_BYTES_MAX = 64 * 2 ** 20
+
+
+def dump_outputs(outdir, env, write_obs, rank=0, world=1):
+    """--dump-outputs: what the last timed step returned to its caller, the
+    env's own ``obs`` [N,15] (unless --no-obs), ``reward`` [N] and ``done`` [N],
+    as ``<outdir>/<name>.npy`` (float32; reward float64 with f64 storage; done
+    as 0.0 / 1.0).  At most 64 MiB over all ranks: a larger batch is cut to a
+    fixed, seeded sample of its lanes (the same lanes in every array, listed
+    in ``sample_rows.npy``).  At N > 1 every rank writes its shard as
+    ``<name>_rank<r>.npy``.  Returns the names written."""
+    import numpy as np
+    import torch
+    arrays = {"reward": env.reward, "done": env.done.to(torch.float32)}
+    if write_obs:
+        arrays["obs"] = env.obs
+    n = env.num_envs
+    row_bytes = sum(a.element_size() * (a.numel() // n) for a in arrays.values())
+    budget = DUMP_BYTES_MAX // world
+    if n * row_bytes > budget:
+        keep = budget // (row_bytes + 8)
+        lanes = np.sort(np.random.default_rng(0).choice(n, size=keep, replace=False))
+        idx = torch.from_numpy(lanes).to(env.device)
+        arrays = {k: a[idx] for k, a in arrays.items()}
+        arrays["sample_rows"] = torch.from_numpy(lanes.astype(np.float64))
+    os.makedirs(outdir, exist_ok=True)
+    suffix = f"_rank{rank}" if world > 1 else ""
+    for name, a in arrays.items():
+        np.save(os.path.join(outdir, f"{name}{suffix}.npy"), a.cpu().numpy())
+    return sorted(arrays)
+
+
 def _free_port() -> int:
     import socket
     with socket.socket() as s:
@@ -886,7 +935,7 @@ def launch_ranks(args) -> int:
             raise SystemExit(f"--gpus {args.gpus} with --dist-backend nccl but {ndev} visible GPUs: "
                              "RCCL needs one GPU per rank")
     cpu_file = None
-    if args.cpu_baseline > 0:
+    if args.full and args.cpu_baseline > 0:
         share = host_cpu_share()
         cpu = cpu_baseline(args.cpu_baseline, args.cpu_workers or share["cores"], args.seed, share)
         fd, cpu_file = tempfile.mkstemp(prefix="dd_cpu_baseline_", suffix=".json")
@@ -925,7 +974,7 @@ def main():
         args.gpus = world
 
     cpu = None
-    if rank == 0 and args.cpu_baseline > 0:
+    if rank == 0 and args.full and args.cpu_baseline > 0:
         # before any GPU call (the legs fork worker processes); at N > 1 under
         # torch.distributed.run the other ranks wait in the rendezvous meanwhile
         share = host_cpu_share()
@@ -1052,13 +1101,18 @@ def main():
             torch.cuda.synchronize(dev)
         wall = time.perf_counter() - t0
     gpu_ms = ev0.elapsed_time(ev1)
-    span_ms = spans.elapsed_ms(0, 1)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, env, write_obs, rank, world)
+    # The kernels' own span is a --full figure: reading it takes a
+    # calibration run of its own.  The two stamps stay in the timed graphs
+    # either way, so a plain run times the same launches.
+    span_ms = spans.elapsed_ms(0, 1) if args.full else 0.0
     # The stamps' own cost (the head stamp's kernel end and the tail stamp's
     # dispatch lie inside the span): an untimed graph of the two stamps
     # alone, replayed after the timed region, measures it and it is
     # subtracted.
     marker_ms = 0.0
-    if G > 0:
+    if args.full and G > 0:
         import statistics
         gc = torch.cuda.CUDAGraph()
         with torch.cuda.stream(stream), torch.cuda.graph(gc, stream=stream):
@@ -1076,20 +1130,20 @@ def main():
     # sanity: the batch is alive and finite
     assert torch.isfinite(env.obs).all().item() and int(env.episode.max()) >= 1
     hbm = None
-    if world == 1 and args.hbm_point > 0:
+    if args.full and world == 1 and args.hbm_point > 0:
         hbm = hbm_point(args.hbm_point, args.precision, args.seed, dev, write_obs)
     gp = None
-    if use_pg:
+    if args.full and use_pg:
         try:  # an optional extra: a failure here must not cost the step measurement
             gp = gather_point(env.obs, n, world, args.dist_backend)
         except Exception as e:  # noqa: BLE001
             gp = {"error": f"{type(e).__name__}: {e}"[:300]}
     c5 = c5a = g5 = c2 = nb = rf = f64p = ppp = pp = pr = pp16 = pr16 = pf = pf16 = sp = rp = None
-    if world == 1 and args.rollout_point > 0:
+    if args.full and world == 1 and args.rollout_point > 0:
         c5 = rollout_point(args.rollout_point, 256, args.precision, args.seed, dev)
         c5a = step_loop_point(args.rollout_point, 256, args.precision, args.seed, dev)
         g5 = gae_point(args.rollout_point, 256, dev)
-    if world == 1 and args.extra_points:
+    if args.full and world == 1 and args.extra_points:
         c2 = config2_point(args.seed, dev)
         nb = notebook_point(n, args.precision, args.seed, dev)
         rf = notebook_point(n, args.precision, args.seed, dev, "reinforce")
@@ -1108,12 +1162,13 @@ def main():
     if rank == 0:
         total_steps = n * pg_world * args.steps
         value = total_steps / wall
-        step_ms = kernel_ms / args.steps  # the K step kernels' own span per launch
+        # the K step kernels' own span per launch (--full: it needs the stamps' calibration run)
+        step_ms = kernel_ms / args.steps if args.full else None
         bytes_env = env.step_bytes_per_env(abi.DD_ACT_BITMASK, with_obs=write_obs)
-        traffic, traffic_note = pmc_traffic_row(n, args.precision, write_obs)
-        achieved = bytes_env * n / (step_ms * 1e-3) / 1e9
+        traffic, traffic_note = pmc_traffic_row(n, args.precision, write_obs) if args.full else (None, None)
+        achieved = bytes_env * n / (step_ms * 1e-3) / 1e9 if args.full else None
         stream_achieved = bytes_env * n / (gpu_ms / args.steps * 1e-3) / 1e9
-        roof = {
+        roof = None if not args.full else {
             "bound": "hbm",
             "achieved": round(achieved, 1),
             "peak": HBM_PEAK_GBS,
@@ -1142,6 +1197,7 @@ def main():
             "n_gpus": pg_world,
             "steps": args.steps,
             "warmup": args.warmup,
+            "full": args.full,
             "ms_per_step": round(wall * 1e3 / args.steps, 6),
             "higher_is_better": True,
             "scaling": "weak",
@@ -1184,7 +1240,7 @@ def main():
             "policy_fused_point_f16x3": pf16,
             "socket_point": sp,
             "render_point": rp,
-            "gpu_ms_per_step": round(step_ms, 6),
+            "gpu_ms_per_step": round(step_ms, 6) if args.full else None,
             "stream_ms_per_step": round(gpu_ms / args.steps, 6),
             "device": torch.cuda.get_device_name(dev),
             "build_info": abi.lib().dd_build_info().decode(),

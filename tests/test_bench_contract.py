@@ -28,6 +28,50 @@ def test_defaults_are_one_gpu_config3(monkeypatch):
     assert a.dist_backend == "nccl"
 
 
+def test_plain_run_is_the_default_and_full_is_an_option(monkeypatch, capsys):
+    import pytest
+    b = _bench()
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "20", "--warmup", "5"])
+    a = b.parse()
+    assert not a.full and not a.dump_outputs and a.steps == 20 and a.warmup == 5
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--dump-outputs", "d"])
+    a = b.parse()
+    assert a.full and a.dump_outputs == "d"
+    for bad in (["--gather-point"], ["--steps", "0"]):  # a --full measurement asked of a plain run; nothing to time
+        monkeypatch.setattr(sys, "argv", ["bench.py"] + bad)
+        with pytest.raises(SystemExit):
+            b.parse()
+    capsys.readouterr()
+
+
+def test_dump_outputs_writes_the_step_outputs(tmp_path, monkeypatch):
+    import types
+    import numpy as np
+    import torch
+    b = _bench()
+    n = 1000
+    g = torch.Generator().manual_seed(3)
+    env = types.SimpleNamespace(num_envs=n, device=torch.device("cpu"), obs=torch.randn(n, 15, generator=g),
+                                reward=torch.randn(n, generator=g, dtype=torch.float64),
+                                done=torch.rand(n, generator=g) < 0.1)
+    assert b.dump_outputs(str(tmp_path / "a"), env, True) == ["done", "obs", "reward"]
+    obs, rew, done = (np.load(tmp_path / "a" / f"{k}.npy") for k in ("obs", "reward", "done"))
+    assert obs.dtype == np.float32 and rew.dtype == np.float64 and done.dtype == np.float32
+    assert np.array_equal(obs, env.obs.numpy()) and np.array_equal(rew, env.reward.numpy())
+    assert np.array_equal(done, env.done.numpy().astype(np.float32))
+    assert b.dump_outputs(str(tmp_path / "b"), env, False, rank=1, world=2) == ["done", "reward"]
+    assert sorted(os.listdir(tmp_path / "b")) == ["done_rank1.npy", "reward_rank1.npy"]
+    # over the byte budget: the same fixed sample of lanes in every array, within the budget, on every call
+    monkeypatch.setattr(b, "DUMP_BYTES_MAX", 8000)
+    for d in ("c", "d"):
+        assert b.dump_outputs(str(tmp_path / d), env, True) == ["done", "obs", "reward", "sample_rows"]
+    got = {k: np.load(tmp_path / "c" / f"{k}.npy") for k in ("obs", "reward", "done", "sample_rows")}
+    lanes = got["sample_rows"].astype(np.int64)
+    assert 0 < len(lanes) < n and np.all(np.diff(lanes) > 0) and sum(v.nbytes for v in got.values()) <= 8000
+    assert np.array_equal(got["obs"], env.obs.numpy()[lanes]) and np.array_equal(got["reward"], env.reward.numpy()[lanes])
+    assert all(np.array_equal(v, np.load(tmp_path / "d" / f"{k}.npy")) for k, v in got.items())
+
+
 def test_cpu_baseline_fields():
     b = _bench()
     r = b.cpu_baseline(0.3, 2, 0)

@@ -23,8 +23,8 @@ def _bench(args, timeout):
 
 
 def test_plain_launch_two_gloo_ranks(gpu_device):
-    r = _bench(["--gpus", "2", "--dist-backend", "gloo", "--steps", "20", "--warmup", "5", "--rollout-point", "0",
-                "--hbm-point", "0", "--no-extra-points", "--cpu-baseline", "1"], timeout=110)
+    r = _bench(["--gpus", "2", "--dist-backend", "gloo", "--steps", "20", "--warmup", "5", "--full", "--rollout-point",
+                "0", "--hbm-point", "0", "--no-extra-points", "--cpu-baseline", "1"], timeout=110)
     assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-3000:])
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1, r.stdout[-2000:]

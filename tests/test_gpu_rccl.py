@@ -8,7 +8,7 @@ socket_server.py:113-124) run over RCCL on device tensors:
     --backend nccl: one rank steps its shard, gathers obs / reward / done /
     every SoA field through RCCL and compares them bit for bit with the same
     frames run as one batch in a fresh child process;
-  * bench.py --dist-backend nccl --gather-point: the process group initialised
+  * bench.py --dist-backend nccl --full --gather-point: the process group initialised
     as at N>1, gather_point timed and checked (its rank-0 block unchanged).
 The 1->8 scaling curve is the driver's (an 8-GPU node); this pins that the
 code path initialises RCCL and moves device tensors correctly on ROCm.
@@ -51,7 +51,7 @@ def test_rccl_gathers_equal_one_batch(tmp_path, gpu_device):
 
 def test_bench_gather_point_over_rccl(gpu_device):
     r = _torchrun([os.path.join(REPO, "bench.py"), "--gpus", "1", "--steps", "20", "--warmup", "5",
-                   "--dist-backend", "nccl", "--gather-point", "--cpu-baseline", "0", "--hbm-point", "0",
+                   "--dist-backend", "nccl", "--full", "--gather-point", "--cpu-baseline", "0", "--hbm-point", "0",
                    "--rollout-point", "0", "--no-extra-points"], timeout=110)
     assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-3000:])
     line = [ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1]

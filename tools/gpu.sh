@@ -10,7 +10,7 @@
 #   tests      pytest -m gpu (PYTEST_K: a -k expression)
 #   smoke      __graft_entry__.smoke()
 #   bench20    the driver's line: bench.py --gpus 1 --steps 20 --warmup 5
-#   bench      bench.py with its defaults (every extra point)
+#   bench      bench.py --full with its defaults (every extra point)
 #   prof20     rocprofv3 --kernel-trace --stats of the driver's exact command (bench.py --gpus 1 --steps 20
 #              --warmup 5) and the trace summary of its 20 timed config-3 launches (c3_k20_trace_summary.json)
 #   prof       rocprofv3 kernel traces: config 3, the 16.8M HBM point, the extra points
@@ -43,7 +43,7 @@ run_step() {
         timeout -k 10 600 python bench.py --gpus 1 --steps 20 --warmup 5 > $OUT/bench_k20.json 2> $OUT/bench_k20.err \
             && cat $OUT/bench_k20.json ;;
     bench)
-        timeout -k 10 600 python bench.py ${BENCHARGS} > $OUT/bench_default.json 2> $OUT/bench_default.err \
+        timeout -k 10 600 python bench.py --full ${BENCHARGS} > $OUT/bench_default.json 2> $OUT/bench_default.err \
             && python3 tools/bench_summary.py $OUT/bench_default.json ;;
     prof20)
         timeout -k 10 600 rocprofv3 --kernel-trace --stats -d $OUT/prof_k20 -o bench -f csv -- python3 bench.py \
@@ -58,7 +58,7 @@ run_step() {
             --envs-per-gpu 16777216 --steps 200 --warmup 20 --cpu-baseline 0 --hbm-point 0 --rollout-point 0 \
             --no-extra-points > $OUT/prof_16m_bench.json 2>> $OUT/prof.err &&
         timeout -k 10 600 rocprofv3 --kernel-trace --stats -d $OUT/prof_extra -o bench -f csv -- python3 bench.py \
-            --steps 200 --warmup 20 --cpu-baseline 0 --hbm-point 0 > $OUT/prof_extra_bench.json 2>> $OUT/prof.err ;;
+            --steps 200 --warmup 20 --full --cpu-baseline 0 --hbm-point 0 > $OUT/prof_extra_bench.json 2>> $OUT/prof.err ;;
     pmc)
         for N in 262144 16777216; do
             for C in FETCH_SIZE WRITE_SIZE; do

@@ -36,7 +36,7 @@ def main():
             env_add, extra = VARIANTS[name]
             env = dict(os.environ, **env_add)
             cmd = [sys.executable, os.path.join(REPO, "bench.py"), "--steps", str(a.steps), "--warmup",
-                   str(a.warmup), "--cpu-baseline", "0", "--hbm-point", "0", "--rollout-point", "0",
+                   str(a.warmup), "--full", "--cpu-baseline", "0", "--hbm-point", "0", "--rollout-point", "0",
                    "--no-extra-points"] + extra
             r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=300)
             if r.returncode != 0:
