@@ -22,6 +22,16 @@
  *   compute_gae               Actor_Critic_PPO.ipynb:733-787          -> dd_gae
  *   collect_episodes_ppo with the actor in the loop
  *                             Actor_Critic_PPO.ipynb:797-917          -> dd_policy_rollout
+ *   evaluate_policy* (temperature / greedy action selection, one episode per
+ *   game, {total_reward, steps, landed, crashed, final_fuel})
+ *                             Actor_Critic_PPO.ipynb:1469-1532 (evaluate_policy),
+ *                             :997-1101 (evaluate_policy_simple; called at T = 0.3, :1388),
+ *                             Actor_Critic_Basic.ipynb:925-988, :638-742,
+ *                             Policy_Gradients.ipynb:879-940, :633-738, :1061-1266
+ *                             (evaluate_policy_live), Policy_Gradients_inference.ipynb:
+ *                             295-356, Actor_Critic_inference.ipynb:229-295, :444-500
+ *                                          -> dd_mlp_forward_sampled (one frame's action)
+ *                                             dd_policy_rollout_sampled (the episode loop)
  *
  * One call processes a batch of N independent drones stored as a
  * struct-of-arrays (SoA) in device memory.  The reference has no FFI of its
@@ -49,7 +59,8 @@
 extern "C" {
 #endif
 
-#define DD_ABI_VERSION 12 /* 12: spawns drawn from Philox4x32-7; 11: shaped_mode (REINFORCE reward), DDRolloutIO.kernel, dd_rollout_kernel,
+#define DD_ABI_VERSION 13 /* 13: DDSampling, DDEpisodeStats, dd_mlp_forward_sampled, dd_policy_rollout_sampled (additions only: the
+                              spawn stream and every existing entry point are ABI 12's); 12: spawns drawn from Philox4x32-7; 11: shaped_mode (REINFORCE reward), DDRolloutIO.kernel, dd_rollout_kernel,
                               dd_device_errors; 10: DDStepIO.state_out (ping-pong state) */
 
 /* Storage precision of the SoA floating-point fields. */
@@ -368,6 +379,40 @@ int dd_mlp_pack(const DDMlpParams *params, int32_t compute, float *packed, void 
 int dd_mlp_forward(const float *packed, int32_t compute, int32_t out_dim,
                    const DDMlpIO *io, int64_t n, void *stream);
 
+/* ---- Action selection of the notebooks' evaluate_policy* cells (ABI 13) -----
+ * Every evaluate_policy, evaluate_policy_simple and evaluate_policy_live picks
+ * its action as
+ *   temperature == 0:  action = probs > 0.5
+ *   else:              q = p^(1/T) / (p^(1/T) + (1-p)^(1/T));  action = Bernoulli(q).sample()
+ * DD_SAMPLE_BERNOULLI  the collection loop's Bernoulli(probs).sample(), as
+ *                      dd_mlp_forward / dd_policy_rollout draw it (T = 1).
+ * DD_SAMPLE_TEMPERED   T > 0 and finite: q_k = Sigmoid(z_k / T) on the last
+ *                      layer's outputs z before the Sigmoid, which is the
+ *                      formula above (p / (1 - p) = e^z) without its float32
+ *                      loss of 1 - p.  The same Philox4x32-10 draw and keying:
+ *                      bit k iff u_k < q_k.  log_prob is
+ *                      Bernoulli(q).log_prob(a).sum(), the distribution drawn
+ *                      from.
+ * DD_SAMPLE_GREEDY     bit k iff p_k > 0.5 on the kernel's own float32 p (what
+ *                      `out` receives); nothing is drawn.  log_prob is that
+ *                      action's log-probability under p. */
+enum { DD_SAMPLE_BERNOULLI = 0, DD_SAMPLE_TEMPERED = 1, DD_SAMPLE_GREEDY = 2 };
+typedef struct DDSampling {
+    int32_t mode;       /* DD_SAMPLE_*                                          */
+    float temperature;  /* DD_SAMPLE_TEMPERED only                              */
+    float *probs_used;  /* nullable; forward: [N][3]; rollout: [frames][N][3]:
+                           the probabilities the draw was compared with (p, q,
+                           or p for DD_SAMPLE_GREEDY)                           */
+} DDSampling;
+
+/* dd_mlp_forward with the action selected by *sampling (actor only).
+ * sampling == NULL is dd_mlp_forward exactly.  hipErrorInvalidValue, before
+ * any launch: an unknown mode, DD_SAMPLE_TEMPERED with a temperature that is
+ * not finite or <= 0, a non-NULL sampling with out_dim == 1. */
+int dd_mlp_forward_sampled(const float *packed, int32_t compute, int32_t out_dim,
+                           const DDMlpIO *io, const DDSampling *sampling, int64_t n,
+                           void *stream);
+
 /* ---- The collection loop with the actor in it --
  * collect_episodes_ppo (Actor_Critic_PPO.ipynb:797-917) for N drones and
  * `frames` frames in one launch: per frame, the actor on the current
@@ -404,6 +449,40 @@ typedef struct DDPolicyRolloutIO {
 int dd_policy_rollout(const DDConfig *cfg, const DDState *st, const float *packed,
                       int32_t compute, const DDPolicyRolloutIO *io, int64_t n,
                       void *stream);
+
+/* Per-lane episode statistics of a policy rollout: the notebooks'
+ * evaluate_policy result {total_reward, steps, landed, crashed, final_fuel}
+ * for every lane.  All four pointers set (or all NULL = no statistics).  They
+ * are in/out accumulators that carry across launches, so a long evaluation
+ * may be chunked; the caller zeroes them before an episode.  A lane adds to
+ * them only while ep_status[i] & DD_ST_DONE is clear at the start of the
+ * frame, so its first episode is counted once, whatever the env does after it
+ * (sticky done or re-spawn).  The flag that ends the episode is the one
+ * done[k] carries: the notebook's done in the notebook reward modes. */
+typedef struct DDEpisodeStats {
+    double *ep_return;  /* [N] sum of the stored reward values (as written to
+                           `reward`, i.e. rounded to the storage precision),
+                           added in double, in frame order                      */
+    int32_t *ep_steps;  /* [N] frames played                                    */
+    uint8_t *ep_status; /* [N] DD_ST_* of the frame that ended the episode
+                           (DD_ST_DONE set), else 0                             */
+    void *ep_fuel;      /* [N] float / double by precision: fuel after the last
+                           frame played                                         */
+} DDEpisodeStats;
+
+/* dd_policy_rollout with the action selected by *sampling (probs_used:
+ * [frames][N][3]) and per-lane episode statistics.  sampling == NULL and
+ * stats == NULL are dd_policy_rollout exactly.  With statistics, io's reward,
+ * done, actions and log_prob may all be NULL: an evaluation then writes no
+ * [frames][N] buffer at all.  The notebooks' evaluation stops at max_steps
+ * without the collection loops' timeout penalty: pass io->max_steps = 0 and
+ * max_steps frames.  hipErrorInvalidValue, before any launch: an unknown
+ * mode, DD_SAMPLE_TEMPERED with a temperature that is not finite or <= 0, a
+ * DDEpisodeStats with some but not all pointers set. */
+int dd_policy_rollout_sampled(const DDConfig *cfg, const DDState *st, const float *packed,
+                              int32_t compute, const DDPolicyRolloutIO *io,
+                              const DDSampling *sampling, const DDEpisodeStats *stats,
+                              int64_t n, void *stream);
 
 /* ---- Rendering -------------------------------------
  * DroneGame.render() in 'rgb_array' mode (game_engine.py:300-337): the scene

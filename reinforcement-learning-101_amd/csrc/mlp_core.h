@@ -523,5 +523,60 @@ __device__ __forceinline__ void actor_sample(const float (&prob)[3], uint64_t en
     lp = fmaf(prob[0] + prob[1] + prob[2], 0.0f, lp);
 }
 
+// Action selection of the notebooks' evaluate_policy* cells (the three
+// *_inference.ipynb, Policy_Gradients.ipynb "Eval", Actor_Critic_PPO.ipynb
+// evaluate_policy):
+//   temperature == 0:  action = probs > 0.5
+//   else:              q = p^(1/T) / (p^(1/T) + (1-p)^(1/T));  action = Bernoulli(q).sample()
+// next to the collection loop's plain draw, as DDSampling's three modes.
+//   DD_SAMPLE_BERNOULLI  actor_sample on prob, as it is.
+//   DD_SAMPLE_TEMPERED   q_k = Sigmoid(z_k / T) from the head's pre-Sigmoid
+//     outputs z.  That IS the notebook's formula: p / (1 - p) = e^z, so
+//     p^(1/T) / (p^(1/T) + (1-p)^(1/T)) = 1 / (1 + (p / (1-p))^(-1/T)) = 1 / (1 +
+//     e^(-z/T)); but the pow form rounds 1 - p in float32 (all of a confident
+//     p's information once p > 1 - 2^-24) and raises that error to the power
+//     1/T, which z / T does not.  (The pow form also turns to 0/0 once both
+//     powers underflow, p = 1/2 first: 2^(-1/T) < 2^-149, i.e. only for T <
+//     ~0.007; Sigmoid(z / T) saturates to 0 or 1 there.)  The draw is
+//     actor_sample's own, against q: the same Philox4x32-10 block and keying,
+//     bit k iff u_k < q_k, and log_prob = Bernoulli(q).log_prob(a).sum(), the
+//     distribution actually drawn from, through the same bernoulli_factor /
+//     logf path with the same NaN propagation.
+//   DD_SAMPLE_GREEDY     bit k iff prob_k > 0.5f on the kernel's own prob (what
+//     `out` receives); no Philox call.  log_prob is that action's
+//     log-probability under prob.
+// used: the probabilities the draw was compared with (p, q, or p for GREEDY).
+// mode is a compile-time constant in dd_mlp_forward_sampled's kernels (one
+// instantiation per mode; the branches fold) and a uniform launch argument in
+// the evaluation rollout (one scalar branch per frame).
+__device__ __forceinline__ void actor_select(int mode, const float (&z)[3], const float (&prob)[3], float temperature,
+                                             uint64_t env, uint64_t step, uint64_t seed, float (&used)[3],
+                                             uint32_t& bits, float& lp) {
+    if (mode == DD_SAMPLE_GREEDY) {
+        bits = 0;
+        float pr = 1.0f;
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            used[k] = prob[k];
+            const bool on = prob[k] > 0.5f;
+            bits |= on ? (1u << k) : 0u;
+            pr *= bernoulli_factor(prob[k], on);
+        }
+        lp = logf(pr);
+        lp = fmaf(prob[0] + prob[1] + prob[2], 0.0f, lp);  // NaN probabilities: a NaN log-probability, as actor_sample
+        return;
+    }
+    if (mode == DD_SAMPLE_TEMPERED) {
+        float zt[3];
+#pragma unroll
+        for (int k = 0; k < 3; ++k) zt[k] = z[k] / temperature;  // IEEE division: z / T rounded once
+        actor_probs(zt, used);
+    } else {
+#pragma unroll
+        for (int k = 0; k < 3; ++k) used[k] = prob[k];
+    }
+    actor_sample(used, env, step, seed, bits, lp);
+}
+
 }  // namespace mlp
 }  // namespace dd

@@ -261,6 +261,15 @@ struct FwdArgs {
     int64_t n;
 };
 
+// dd_mlp_forward_sampled's launch: FwdArgs and the DDSampling fields, the mode
+// as the type (mlp_kernel is a template over its argument type: an
+// instantiation of its own per mode).
+template <int kMode>
+struct SampledArgs : FwdArgs {
+    float temperature;
+    float* probs_used;
+};
+
 // Layer 1's B operands for lane (c, h) of a tile: obs[d][8h + q] (kSplit) or
 // obs[d][2q + h], zero past column 14 and past the last row.
 template <bool kSplit>
@@ -314,6 +323,31 @@ __device__ __forceinline__ void emit_outputs(const FwdArgs& p, int64_t d, const 
             actor_sample(prob, (uint64_t)(p.env_id_base + d), (uint64_t)p.step, p.seed, bits, lp);
             if (p.actions) p.actions[d] = (uint8_t)bits;
             if (p.log_prob) p.log_prob[d] = lp;
+        }
+    }
+}
+
+// The actor's outputs of one drone with the action selected by kMode
+// (mlp_core.h actor_select).
+template <int K, int kMode>
+__device__ __forceinline__ void emit_outputs(const SampledArgs<kMode>& p, int64_t d, const float (&z)[K]) {
+    static_assert(K == 3, "action selection is the actor's");
+    float prob[3];
+    actor_probs(z, prob);
+    if (p.out) {
+#pragma unroll
+        for (int k = 0; k < 3; ++k) p.out[d * 3 + k] = prob[k];
+    }
+    if (p.actions || p.log_prob || p.probs_used) {
+        uint32_t bits;
+        float lp, used[3];
+        actor_select(kMode, z, prob, p.temperature, (uint64_t)(p.env_id_base + d), (uint64_t)p.step, p.seed, used,
+                            bits, lp);
+        if (p.actions) p.actions[d] = (uint8_t)bits;
+        if (p.log_prob) p.log_prob[d] = lp;
+        if (p.probs_used) {
+#pragma unroll
+            for (int k = 0; k < 3; ++k) p.probs_used[d * 3 + k] = used[k];
         }
     }
 }
@@ -408,8 +442,10 @@ __device__ __forceinline__ void wait_layers23() {
     __builtin_amdgcn_s_barrier();
 }
 
-template <int K, bool kSplit>
-__global__ __launch_bounds__(kThreads) void mlp_kernel(const float* __restrict__ packed, FwdArgs p) {
+// A: FwdArgs (dd_mlp_forward: the instructions it had before the action
+// selection existed) or SampledArgs<mode> (dd_mlp_forward_sampled, K = 3).
+template <int K, bool kSplit, typename A>
+__global__ __launch_bounds__(kThreads) void mlp_kernel(const float* __restrict__ packed, A p) {
     extern __shared__ f32x4 lds4[];
     const float* lds = reinterpret_cast<const float*>(lds4);
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, h = lane >> 5, c = lane & 31;
@@ -444,11 +480,11 @@ __global__ __launch_bounds__(kThreads) void mlp_kernel(const float* __restrict__
     }
 }
 
-template <int K, bool kSplit>
-hipError_t launch(const float* packed, const FwdArgs& a, hipStream_t s) {
+template <int K, bool kSplit, typename A>
+hipError_t launch(const float* packed, const A& a, hipStream_t s) {
     // the LDS image exceeds the 64 KB default; the attribute is per device, so
     // it is set on every launch (a cheap host call) rather than once per process
-    const hipError_t e = hipFuncSetAttribute((const void*)mlp_kernel<K, kSplit>,
+    const hipError_t e = hipFuncSetAttribute((const void*)mlp_kernel<K, kSplit, A>,
                                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsPad);
     if (e != hipSuccess) return e;
     int dev = 0, cus = 256;
@@ -457,8 +493,26 @@ hipError_t launch(const float* packed, const FwdArgs& a, hipStream_t s) {
     const int64_t tiles = (a.n + kCols - 1) / kCols;
     const int64_t want = (tiles + kWaves - 1) / kWaves;
     const unsigned blocks = (unsigned)(want < cus ? want : cus);  // one block per CU, waves loop over tiles
-    hipLaunchKernelGGL((mlp_kernel<K, kSplit>), dim3(blocks), dim3(kThreads), kLdsPad, s, packed, a);
+    hipLaunchKernelGGL((mlp_kernel<K, kSplit, A>), dim3(blocks), dim3(kThreads), kLdsPad, s, packed, a);
     return hipGetLastError();
+}
+
+template <bool kSplit, int kMode>
+hipError_t launch_sampled(const float* packed, const FwdArgs& a, const DDSampling& sm, hipStream_t s) {
+    SampledArgs<kMode> p;
+    static_cast<FwdArgs&>(p) = a;
+    p.temperature = sm.temperature;
+    p.probs_used = sm.probs_used;
+    return launch<3, kSplit>(packed, p, s);
+}
+
+template <bool kSplit>
+hipError_t launch_sampled(const float* packed, const FwdArgs& a, const DDSampling& sm, hipStream_t s) {
+    switch (sm.mode) {
+        case DD_SAMPLE_TEMPERED: return launch_sampled<kSplit, DD_SAMPLE_TEMPERED>(packed, a, sm, s);
+        case DD_SAMPLE_GREEDY: return launch_sampled<kSplit, DD_SAMPLE_GREEDY>(packed, a, sm, s);
+        default: return launch_sampled<kSplit, DD_SAMPLE_BERNOULLI>(packed, a, sm, s);
+    }
 }
 
 }  // namespace mlp
@@ -485,7 +539,20 @@ int dd_mlp_pack(const DDMlpParams* p, int32_t compute, float* packed, void* stre
 
 int dd_mlp_forward(const float* packed, int32_t compute, int32_t out_dim, const DDMlpIO* io, int64_t n,
                    void* stream) {
+    return dd_mlp_forward_sampled(packed, compute, out_dim, io, nullptr, n, stream);
+}
+
+int dd_mlp_forward_sampled(const float* packed, int32_t compute, int32_t out_dim, const DDMlpIO* io,
+                           const DDSampling* sampling, int64_t n, void* stream) {
     if (!io || n < 0 || !(out_dim == 1 || out_dim == 3)) return hipErrorInvalidValue;
+    if (sampling) {
+        if (out_dim == 1) return hipErrorInvalidValue;  // the critic selects no action
+        if (sampling->mode != DD_SAMPLE_BERNOULLI && sampling->mode != DD_SAMPLE_TEMPERED &&
+            sampling->mode != DD_SAMPLE_GREEDY)
+            return hipErrorInvalidValue;
+        if (sampling->mode == DD_SAMPLE_TEMPERED && !(sampling->temperature > 0.0f && isfinite(sampling->temperature)))
+            return hipErrorInvalidValue;
+    }
     if (compute != DD_MLP_F32 && compute != DD_MLP_F16X3) return hipErrorInvalidValue;
     if (n == 0) return hipSuccess;
     if (!packed || !io->obs) return hipErrorInvalidValue;
@@ -493,6 +560,10 @@ int dd_mlp_forward(const float* packed, int32_t compute, int32_t out_dim, const 
     if (out_dim == 1 && (io->actions || io->log_prob)) return hipErrorInvalidValue;  // nothing to sample
     const dd::mlp::FwdArgs a{io->obs, io->out, io->actions, io->log_prob, io->seed, io->step, io->env_id_base, n};
     const hipStream_t s = (hipStream_t)stream;
+    // the plain Bernoulli draw with no probs_used is dd_mlp_forward's own kernel
+    if (sampling && (sampling->mode != DD_SAMPLE_BERNOULLI || sampling->probs_used))
+        return compute == DD_MLP_F16X3 ? dd::mlp::launch_sampled<true>(packed, a, *sampling, s)
+                                       : dd::mlp::launch_sampled<false>(packed, a, *sampling, s);
     if (compute == DD_MLP_F16X3)
         return out_dim == 3 ? dd::mlp::launch<3, true>(packed, a, s) : dd::mlp::launch<1, true>(packed, a, s);
     return out_dim == 3 ? dd::mlp::launch<3, false>(packed, a, s) : dd::mlp::launch<1, false>(packed, a, s);

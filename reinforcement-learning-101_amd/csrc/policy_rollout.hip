@@ -33,7 +33,10 @@
 // which a gfx950 SIMD does not overlap); the frame adds ~3 % to a wave's
 // cycles (SQ counters).
 #include <hip/hip_runtime.h>
+#include <math.h>
 #include <stdint.h>
+
+#include <type_traits>
 
 #include "dronestep.h"
 #include "frame.h"
@@ -72,6 +75,23 @@ struct Args {
     int32_t shape;         // kShapeNone / kShapePpo / kShapeReinforce (frame.h)
     int32_t rows_aligned;  // every frame's obs rows start 16-byte aligned (obs aligned, n % 4 == 0)
     int32_t final_aligned; // obs_final 16-byte aligned
+};
+
+// dd_policy_rollout_sampled's launch: Args, DDSampling and DDEpisodeStats.  A
+// type of its own: the kernel is a template over its argument type, so the
+// evaluation kernels (policy_rollout_kernel<..., EvalArgs>) are instantiations
+// apart, and the collection kernel (<..., Args>: DD_SAMPLE_BERNOULLI, no
+// statistics, every per-frame buffer), which sits at its register cap
+// (mlp_core.h), compiles to the instructions it had before the evaluation
+// existed.  With statistics, reward, done, actions and log_prob may be null.
+struct EvalArgs : Args {
+    int32_t mode;          // DD_SAMPLE_* (uniform: one branch per frame)
+    float temperature;
+    float* probs_used;     // [frames][n][3] or null
+    double* ep_return;     // DDEpisodeStats: all four or none
+    int32_t* ep_steps;
+    uint8_t* ep_status;
+    void* ep_fuel;
 };
 
 // Observation column `col` of layer 1's B operand for lane half h: column
@@ -122,9 +142,10 @@ __device__ __forceinline__ void next_input(const Consts& k, const Lane& s, int h
     for (int q = 0; q < 8; ++q) x[q] = h ? o[in_col<kSplit>(q, 1)] : o[in_col<kSplit>(q, 0)];
 }
 
-template <typename T, bool kSplit, bool kRef>
-__global__ __launch_bounds__(kThreads) void policy_rollout_kernel(const float* __restrict__ packed, Args p,
+template <typename T, bool kSplit, bool kRef, typename P>
+__global__ __launch_bounds__(kThreads) void policy_rollout_kernel(const float* __restrict__ packed, P p,
                                                                   Soa<T> a) {
+    constexpr bool kEval = std::is_same<P, EvalArgs>::value;
     extern __shared__ f32x4 lds4[];
     float* lds = reinterpret_cast<float*>(lds4);
     for (int i = threadIdx.x; i < kPacked / 4; i += kThreads)
@@ -159,6 +180,20 @@ __global__ __launch_bounds__(kThreads) void policy_rollout_kernel(const float* _
         const int col = in_col<kSplit>(q, h);
         x[q] = col < DD_OBS_DIM ? p.obs0[d * DD_OBS_DIM + col] : 0.0f;
     }
+    // DDEpisodeStats of this lane, in registers across the launch's frames
+    double ep_return = 0.0, ep_fuel = 0.0;
+    int32_t ep_steps = 0;
+    uint32_t ep_status = 0;
+    bool stats = false;
+    if constexpr (kEval) {
+        stats = p.ep_return != nullptr;
+        if (stats) {
+            ep_return = p.ep_return[d];
+            ep_steps = p.ep_steps[d];
+            ep_status = p.ep_status[d];
+            ep_fuel = (double)static_cast<const T*>(p.ep_fuel)[d];
+        }
+    }
 
     for (int f = 0; f < p.frames; ++f) {
         const int64_t fo = (int64_t)f * p.n;  // frame offset of [frames][n] buffers
@@ -171,7 +206,17 @@ __global__ __launch_bounds__(kThreads) void policy_rollout_kernel(const float* _
         mlp::actor_probs(z, prob);
         uint32_t act;
         float lp;
-        mlp::actor_sample(prob, (uint64_t)env, (uint64_t)(p.step + f), p.seed, act, lp);
+        if constexpr (kEval) {  // DDSampling's action selection (mlp_core.h actor_select)
+            float used[3];
+            mlp::actor_select(p.mode, z, prob, p.temperature, (uint64_t)env, (uint64_t)(p.step + f), p.seed, used, act,
+                              lp);
+            if (writer && p.probs_used) {
+#pragma unroll
+                for (int j = 0; j < 3; ++j) __builtin_nontemporal_store(used[j], &p.probs_used[(fo + d) * 3 + j]);
+            }
+        } else {
+            mlp::actor_sample(prob, (uint64_t)env, (uint64_t)(p.step + f), p.seed, act, lp);
+        }
         if (writer) {
             if (p.actions) __builtin_nontemporal_store((uint8_t)act, &p.actions[fo + d]);
             if (p.log_prob) __builtin_nontemporal_store(lp, &p.log_prob[fo + d]);
@@ -196,6 +241,8 @@ __global__ __launch_bounds__(kThreads) void policy_rollout_kernel(const float* _
         }
         T* rew = reinterpret_cast<T*>(p.reward) + fo + d;
         uint8_t* dn = p.done + fo + d;
+        T ep_rew = (T)0;       // the frame's stored reward and done flag, for the statistics
+        bool ep_done = false;
         if (shaped) {  // dd_step's notebook path (PPO: the history in h0 / h1)
             double v[13];
             observe_values<kGuard, true>(k, s, v);  // the notebook reward's doubles: exact quotients
@@ -223,20 +270,39 @@ __global__ __launch_bounds__(kThreads) void policy_rollout_kernel(const float* _
                     s.status |= DD_ST_DONE;
                 }
             }
+            if constexpr (kEval) {
+                ep_rew = (T)sr;
+                ep_done = sd;
+            }
             if (writer) {
-                __builtin_nontemporal_store((T)sr, rew);
-                __builtin_nontemporal_store((uint8_t)(sd ? 1 : 0), dn);
+                if (!kEval || p.reward) __builtin_nontemporal_store((T)sr, rew);
+                if (!kEval || p.done) __builtin_nontemporal_store((uint8_t)(sd ? 1 : 0), dn);
                 if (p.engine_reward) {
                     __builtin_nontemporal_store((T)reward, reinterpret_cast<T*>(p.engine_reward) + fo + d);
                     __builtin_nontemporal_store((uint8_t)((s.status & DD_ST_DONE) ? 1 : 0), p.engine_done + fo + d);
                 }
             }
-        } else if (writer) {
-            __builtin_nontemporal_store((T)reward, rew);
-            __builtin_nontemporal_store((uint8_t)((s.status & DD_ST_DONE) ? 1 : 0), dn);
+        } else {
+            if constexpr (kEval) {
+                ep_rew = (T)reward;
+                ep_done = (s.status & DD_ST_DONE) != 0;
+            }
+            if (writer) {
+                if (!kEval || p.reward) __builtin_nontemporal_store((T)reward, rew);
+                if (!kEval || p.done) __builtin_nontemporal_store((uint8_t)((s.status & DD_ST_DONE) ? 1 : 0), dn);
+            }
         }
         next_input<kRef, kGuard, kSplit>(k, s, h, x);  // from the unrounded frame, like dd_step's obs
         quantize<T, kRef>(s);
+        if constexpr (kEval) {
+            // the lane's first episode, counted once: only while no frame has ended it
+            if (stats && !(ep_status & DD_ST_DONE)) {
+                ep_return += (double)ep_rew;  // the stored value, in frame order
+                ep_steps += 1;
+                ep_fuel = (double)(T)s.fuel;
+                if (ep_done) ep_status = s.status | DD_ST_DONE;
+            }
+        }
     }
 
     if (p.obs_final) store_rows<kSplit>(slice, x, c, h, rows, p.obs_final + d0 * DD_OBS_DIM, p.final_aligned);
@@ -245,25 +311,45 @@ __global__ __launch_bounds__(kThreads) void policy_rollout_kernel(const float* _
         a.omega[d] = (T)s.omega; a.fuel[d] = (T)s.fuel; a.px[d] = (T)s.px; a.py[d] = (T)s.py;
         a.total[d] = (T)s.total; a.status[d] = (uint8_t)s.status; a.steps[d] = s.steps; a.episode[d] = s.episode;
         if (ppo) { p.shaped_hist[d] = h0; p.shaped_hist[p.n + d] = h1; }
+        if constexpr (kEval) {
+            if (stats) {
+                p.ep_return[d] = ep_return;
+                p.ep_steps[d] = ep_steps;
+                p.ep_status[d] = (uint8_t)ep_status;
+                static_cast<T*>(p.ep_fuel)[d] = (T)ep_fuel;
+            }
+        }
     }
 }
 
-template <typename T, bool kSplit, bool kRef>
-hipError_t launch(const float* packed, const Args& p, const Soa<T>& a, hipStream_t s) {
+template <typename T, bool kSplit, bool kRef, typename P>
+hipError_t launch(const float* packed, const P& p, const Soa<T>& a, hipStream_t s) {
     // the LDS image exceeds the 64 KB default; per device, so set on every launch
-    const hipError_t e = hipFuncSetAttribute((const void*)policy_rollout_kernel<T, kSplit, kRef>,
+    const hipError_t e = hipFuncSetAttribute((const void*)policy_rollout_kernel<T, kSplit, kRef, P>,
                                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsBytes);
     if (e != hipSuccess) return e;
     const int64_t tiles = (p.n + kCols - 1) / kCols;
     const unsigned blocks = (unsigned)((tiles + kWaves - 1) / kWaves);  // one wave per 32-drone tile
-    hipLaunchKernelGGL((policy_rollout_kernel<T, kSplit, kRef>), dim3(blocks), dim3(kThreads), kLdsBytes, s, packed,
-                       p, a);
+    hipLaunchKernelGGL((policy_rollout_kernel<T, kSplit, kRef, P>), dim3(blocks), dim3(kThreads), kLdsBytes, s,
+                       packed, p, a);
     return hipGetLastError();
 }
 
-template <typename T, bool kSplit>
-hipError_t launch_ref(bool ref, const float* packed, const Args& p, const Soa<T>& a, hipStream_t s) {
+template <typename T, bool kSplit, typename P>
+hipError_t launch_ref(bool ref, const float* packed, const P& p, const Soa<T>& a, hipStream_t s) {
     return ref ? launch<T, kSplit, true>(packed, p, a, s) : launch<T, kSplit, false>(packed, p, a, s);
+}
+
+template <typename P>
+hipError_t launch_any(const DDState& st, int32_t compute, bool ref, const float* packed, const P& p, hipStream_t s) {
+    if (st.precision == DD_F64) {
+        const Soa<double> a = soa_of<double>(st, 0);
+        return compute == DD_MLP_F16X3 ? launch_ref<double, true>(ref, packed, p, a, s)
+                                       : launch_ref<double, false>(ref, packed, p, a, s);
+    }
+    const Soa<float> a = soa_of<float>(st, 0);
+    return compute == DD_MLP_F16X3 ? launch_ref<float, true>(ref, packed, p, a, s)
+                                   : launch_ref<float, false>(ref, packed, p, a, s);
 }
 
 }  // namespace prl
@@ -271,7 +357,27 @@ hipError_t launch_ref(bool ref, const float* packed, const Args& p, const Soa<T>
 
 extern "C" int dd_policy_rollout(const DDConfig* cfg, const DDState* st, const float* packed, int32_t compute,
                                  const DDPolicyRolloutIO* io, int64_t n, void* stream) {
+    return dd_policy_rollout_sampled(cfg, st, packed, compute, io, nullptr, nullptr, n, stream);
+}
+
+extern "C" int dd_policy_rollout_sampled(const DDConfig* cfg, const DDState* st, const float* packed,
+                                         int32_t compute, const DDPolicyRolloutIO* io, const DDSampling* sampling,
+                                         const DDEpisodeStats* stats, int64_t n, void* stream) {
     if (!cfg || !io || !dd::state_ok(st) || n < 0 || io->frames < 0) return hipErrorInvalidValue;
+    if (sampling) {
+        if (sampling->mode != DD_SAMPLE_BERNOULLI && sampling->mode != DD_SAMPLE_TEMPERED &&
+            sampling->mode != DD_SAMPLE_GREEDY)
+            return hipErrorInvalidValue;
+        if (sampling->mode == DD_SAMPLE_TEMPERED && !(sampling->temperature > 0.0f && isfinite(sampling->temperature)))
+            return hipErrorInvalidValue;
+    }
+    bool with_stats = false;
+    if (stats) {  // all four, or none (= no statistics)
+        const int set = (stats->ep_return != nullptr) + (stats->ep_steps != nullptr) + (stats->ep_status != nullptr) +
+                        (stats->ep_fuel != nullptr);
+        if (set != 0 && set != 4) return hipErrorInvalidValue;
+        with_stats = set == 4;
+    }
     if (compute != DD_MLP_F32 && compute != DD_MLP_F16X3) return hipErrorInvalidValue;
     if ((io->engine_reward == nullptr) != (io->engine_done == nullptr)) return hipErrorInvalidValue;
     if (io->shaped_mode != DD_SHAPED_PPO && io->shaped_mode != DD_SHAPED_REINFORCE) return hipErrorInvalidValue;
@@ -279,7 +385,9 @@ extern "C" int dd_policy_rollout(const DDConfig* cfg, const DDState* st, const f
                       : io->shaped_hist ? dd::kShapePpo : dd::kShapeNone;
     if (io->engine_reward && shape == dd::kShapeNone) return hipErrorInvalidValue;
     if (n == 0) return hipSuccess;
-    if (!packed || !io->obs0 || (io->frames > 0 && (!io->reward || !io->done))) return hipErrorInvalidValue;
+    // the per-frame buffers are optional only next to the statistics
+    if (!packed || !io->obs0 || (io->frames > 0 && !with_stats && (!io->reward || !io->done)))
+        return hipErrorInvalidValue;
     if (reinterpret_cast<uintptr_t>(packed) & 15u) return hipErrorInvalidValue;  // read as 16-byte fragments
     if (io->frames == 0 && io->obs_final == nullptr) return hipSuccess;
     dd::prl::Args p{};
@@ -304,15 +412,19 @@ extern "C" int dd_policy_rollout(const DDConfig* cfg, const DDState* st, const f
     p.final_aligned = (reinterpret_cast<uintptr_t>(io->obs_final) & 15u) == 0;
     const bool ref = dd::uses_reference_physics(*cfg);
     const hipStream_t s = (hipStream_t)stream;
-    hipError_t e;
-    if (st->precision == DD_F64) {
-        const dd::Soa<double> a = dd::soa_of<double>(*st, 0);
-        e = compute == DD_MLP_F16X3 ? dd::prl::launch_ref<double, true>(ref, packed, p, a, s)
-                                    : dd::prl::launch_ref<double, false>(ref, packed, p, a, s);
-    } else {
-        const dd::Soa<float> a = dd::soa_of<float>(*st, 0);
-        e = compute == DD_MLP_F16X3 ? dd::prl::launch_ref<float, true>(ref, packed, p, a, s)
-                                    : dd::prl::launch_ref<float, false>(ref, packed, p, a, s);
+    // the plain Bernoulli draw with no probs_used and no statistics is the collection kernel
+    const bool eval = with_stats || (sampling && (sampling->mode != DD_SAMPLE_BERNOULLI || sampling->probs_used));
+    if (!eval) return (int)dd::prl::launch_any(*st, compute, ref, packed, p, s);
+    dd::prl::EvalArgs q{};
+    static_cast<dd::prl::Args&>(q) = p;
+    q.mode = sampling ? sampling->mode : DD_SAMPLE_BERNOULLI;
+    q.temperature = sampling ? sampling->temperature : 1.0f;
+    q.probs_used = sampling ? sampling->probs_used : nullptr;
+    if (with_stats) {
+        q.ep_return = stats->ep_return;
+        q.ep_steps = stats->ep_steps;
+        q.ep_status = stats->ep_status;
+        q.ep_fuel = stats->ep_fuel;
     }
-    return (int)e;
+    return (int)dd::prl::launch_any(*st, compute, ref, packed, q, s);
 }

@@ -6,7 +6,9 @@ gfx950 behind a C ABI (``include/dronestep.h``), with a gym-style batched
 surface (:class:`VecDroneEnv`) and the reference's per-game APIs
 (:class:`DroneGameClient`, :class:`DroneGame`) on top; the notebooks'
 policy / value networks (:class:`MlpNet`, f32 MFMA) and GAE (:func:`gae`)
-for on-device collection.
+for on-device collection, and the notebooks' ``evaluate_policy`` (temperature
+or greedy action selection, one episode per lane:
+:meth:`VecDroneEnv.evaluate_policy`).
 """
 from .config import EnvConfig
 from .vec_env import OBS_KEYS, StepInfo, VecDroneEnv

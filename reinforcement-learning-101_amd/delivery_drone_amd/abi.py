@@ -18,11 +18,13 @@ __all__ = [
     "DD_RENDER_HUD", "DD_RENDER_GAME_OVER", "DD_MLP_F32", "DD_MLP_F16X3",
     "DD_SHAPED_PPO", "DD_SHAPED_REINFORCE", "DD_ROLLOUT_AUTO", "DD_ROLLOUT_SINGLE", "DD_ROLLOUT_SPLIT_NO_WAIT",
     "DD_ROLLOUT_FLUSHED", "DD_ROLLOUT_HELD", "DD_ROLLOUT_SPLIT", "DD_ERR_HANDOVER",
-    "DDConfig", "DDState", "DDStepIO", "DDRolloutIO", "DDMlpParams", "DDMlpIO", "DDPolicyRolloutIO", "lib", "load", "library_path", "check",
+    "DD_SAMPLE_BERNOULLI", "DD_SAMPLE_TEMPERED", "DD_SAMPLE_GREEDY",
+    "DDConfig", "DDState", "DDStepIO", "DDRolloutIO", "DDMlpParams", "DDMlpIO", "DDPolicyRolloutIO", "DDSampling",
+    "DDEpisodeStats", "sampling_mode", "lib", "load", "library_path", "check",
     "NativeLibraryError",
 ]
 
-DD_ABI_VERSION = 12
+DD_ABI_VERSION = 13
 DD_F32, DD_F64 = 0, 1
 DD_ACT_BITMASK, DD_ACT_F32X3, DD_ACT_U8X3, DD_ACT_PHILOX = 0, 1, 2, 3
 DD_ST_DONE, DD_ST_LANDED, DD_ST_CRASHED, DD_ST_PLAT_LEFT = 1, 2, 4, 8
@@ -34,6 +36,7 @@ DD_ROLLOUT_AUTO, DD_ROLLOUT_SINGLE, DD_ROLLOUT_SPLIT_NO_WAIT = 0, 1, 2
 DD_ROLLOUT_FLUSHED, DD_ROLLOUT_HELD, DD_ROLLOUT_SPLIT = 16, 17, 18
 DD_ERR_HANDOVER = 1
 DD_MEM_DEFAULT, DD_MEM_CONTIGUOUS = 0, 1
+DD_SAMPLE_BERNOULLI, DD_SAMPLE_TEMPERED, DD_SAMPLE_GREEDY = 0, 1, 2
 
 _D = ctypes.c_double
 _I = ctypes.c_int32
@@ -125,6 +128,30 @@ class DDPolicyRolloutIO(ctypes.Structure):
     ]
 
 
+class DDSampling(ctypes.Structure):
+    _fields_ = [("mode", _I), ("temperature", ctypes.c_float), ("probs_used", ctypes.c_void_p)]
+
+
+class DDEpisodeStats(ctypes.Structure):
+    _fields_ = [("ep_return", ctypes.c_void_p), ("ep_steps", ctypes.c_void_p), ("ep_status", ctypes.c_void_p),
+                ("ep_fuel", ctypes.c_void_p)]
+
+
+def sampling_mode(temperature) -> int:
+    """The ``DD_SAMPLE_*`` mode of a notebook ``temperature``: 1 is the plain
+    Bernoulli draw, 0 greedy (``probs > 0.5``), any other positive finite value
+    the tempered draw; anything else raises ``ValueError``."""
+    try:
+        t = float(temperature)
+    except (TypeError, ValueError):
+        raise ValueError(f"temperature must be a number, got {temperature!r}") from None
+    if t == 0.0:
+        return DD_SAMPLE_GREEDY
+    if not (0.0 < t < float("inf")):
+        raise ValueError(f"temperature must be 0 (greedy) or positive and finite, got {temperature!r}")
+    return DD_SAMPLE_BERNOULLI if t == 1.0 else DD_SAMPLE_TEMPERED
+
+
 #: every symbol include/dronestep.h declares, with its ctypes signature
 EXPORTS = {
     "dd_config_default": (None, [ctypes.POINTER(DDConfig)]),
@@ -154,6 +181,11 @@ EXPORTS = {
                                       ctypes.c_void_p]),
     "dd_policy_rollout": (ctypes.c_int, [ctypes.POINTER(DDConfig), ctypes.POINTER(DDState), ctypes.c_void_p, _I,
                                          ctypes.POINTER(DDPolicyRolloutIO), ctypes.c_int64, ctypes.c_void_p]),
+    "dd_mlp_forward_sampled": (ctypes.c_int, [ctypes.c_void_p, _I, _I, ctypes.POINTER(DDMlpIO),
+                                              ctypes.POINTER(DDSampling), ctypes.c_int64, ctypes.c_void_p]),
+    "dd_policy_rollout_sampled": (ctypes.c_int, [ctypes.POINTER(DDConfig), ctypes.POINTER(DDState), ctypes.c_void_p,
+                                                 _I, ctypes.POINTER(DDPolicyRolloutIO), ctypes.POINTER(DDSampling),
+                                                 ctypes.POINTER(DDEpisodeStats), ctypes.c_int64, ctypes.c_void_p]),
     "dd_render": (ctypes.c_int, [ctypes.POINTER(DDConfig), ctypes.POINTER(DDState), ctypes.c_void_p,
                                  ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_void_p, _I,
                                  ctypes.c_void_p]),
@@ -171,7 +203,8 @@ EXPORTS = {
 #: symbols a timing-only lab build (tools/build_variants.sh) or an older
 #: committed source built for an A/B run may lack
 _LAB_OPTIONAL = ("dd_build_info", "dd_selftest_sqrt", "dd_rollout_kernel", "dd_device_errors", "dd_stamp",
-                 "dd_wall_clock_khz", "dd_device_alloc", "dd_device_free")
+                 "dd_wall_clock_khz", "dd_device_alloc", "dd_device_free", "dd_mlp_forward_sampled",
+                 "dd_policy_rollout_sampled")
 
 
 class NativeLibraryError(RuntimeError):

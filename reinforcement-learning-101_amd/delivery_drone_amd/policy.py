@@ -113,11 +113,16 @@ class MlpNet:
             raise ValueError(f"obs is on {obs.device}, the network on {self.device}")
         return obs.to(torch.float32).contiguous()
 
-    def _run(self, obs, out=None, actions=None, log_prob=None, seed=0, step=0, env_id_base=0):
+    def _run(self, obs, out=None, actions=None, log_prob=None, seed=0, step=0, env_id_base=0, sampling=None):
         io = abi.DDMlpIO(obs.data_ptr(), out.data_ptr() if out is not None else None,
                          actions.data_ptr() if actions is not None else None,
                          log_prob.data_ptr() if log_prob is not None else None,
                          int(seed) & (2 ** 64 - 1), int(step), int(env_id_base))
+        if sampling is not None:
+            abi.check(self._lib.dd_mlp_forward_sampled(self.packed.data_ptr(), self._mode, self.out_dim,
+                                                       ctypes.byref(io), ctypes.byref(sampling), obs.shape[0],
+                                                       self._stream()), "dd_mlp_forward_sampled")
+            return
         abi.check(self._lib.dd_mlp_forward(self.packed.data_ptr(), self._mode, self.out_dim, ctypes.byref(io),
                                            obs.shape[0], self._stream()), "dd_mlp_forward")
 
@@ -132,7 +137,8 @@ class MlpNet:
 
     def act(self, obs: torch.Tensor, *, seed: int = 0, step: int = 0, env_id_base: int = 0,
             probs: bool = False, actions_out: Optional[torch.Tensor] = None,
-            log_prob_out: Optional[torch.Tensor] = None):
+            log_prob_out: Optional[torch.Tensor] = None, temperature: float = 1.0,
+            probs_used_out: Optional[torch.Tensor] = None):
         """Sample actions as the collection loop does (actor only).
 
         Returns ``(actions, log_prob)`` or ``(actions, log_prob, probs)``:
@@ -140,14 +146,35 @@ class MlpNet:
         1 left, 2 right), log_prob the float32 ``[N]`` sum over the three
         Bernoulli factors.  Draws are Philox4x32-10 keyed by (seed; env id,
         step), so a lane's sample does not depend on sharding.
+
+        ``temperature`` is the notebooks' ``evaluate_policy`` argument
+        (``dd_mlp_forward_sampled``): 1 (default) the plain
+        ``Bernoulli(probs).sample()``; 0 greedy, ``probs > 0.5``, with no
+        draw; any other positive finite value draws from ``q = p**(1/T) /
+        (p**(1/T) + (1-p)**(1/T))``, evaluated as ``sigmoid(z / T)`` on the
+        network's pre-Sigmoid outputs, and ``log_prob`` is then that of
+        ``Bernoulli(q)``.  ``probs_used_out`` (float32 ``[N, 3]``) receives the
+        probabilities the draw was compared with (``p``, ``q``, or ``p`` when
+        greedy); ``probs=True`` returns the network's own ``p`` in every mode.
         """
         if self.out_dim != 3:
             raise ValueError("act() needs the actor (out_dim 3)")
+        mode = abi.sampling_mode(temperature)
         obs = self._obs(obs)
         n = obs.shape[0]
+        sampling = None
+        if mode != abi.DD_SAMPLE_BERNOULLI or probs_used_out is not None:
+            if probs_used_out is not None and (
+                    tuple(probs_used_out.shape) != (n, 3) or probs_used_out.dtype != torch.float32
+                    or not probs_used_out.is_contiguous() or probs_used_out.device != self.device):
+                raise ValueError(f"probs_used_out must be a contiguous float32 tensor of shape ({n}, 3) "
+                                 f"on {self.device}")
+            sampling = abi.DDSampling(mode, float(temperature),
+                                      probs_used_out.data_ptr() if probs_used_out is not None else None)
         actions = actions_out if actions_out is not None else torch.empty(n, dtype=torch.uint8, device=self.device)
         log_prob = log_prob_out if log_prob_out is not None else torch.empty(n, dtype=torch.float32,
                                                                              device=self.device)
         p = torch.empty(n, 3, dtype=torch.float32, device=self.device) if probs else None
-        self._run(obs, out=p, actions=actions, log_prob=log_prob, seed=seed, step=step, env_id_base=env_id_base)
+        self._run(obs, out=p, actions=actions, log_prob=log_prob, seed=seed, step=step, env_id_base=env_id_base,
+                  sampling=sampling)
         return (actions, log_prob, p) if probs else (actions, log_prob)
