@@ -1,9 +1,10 @@
 // frame.h — one drone's frame of DroneGame.step in IEEE double: world
 // constants, the lane state, Drone.apply_thrust / update, the reward cascade,
 // get_state's observation row and the notebooks' calc_reward.  Shared by the
-// step / rollout kernels (drone_step.hip) and the fused policy rollout
+// step / rollout kernels (step.hip, rollout.hip) and the fused policy rollout
 // (policy_rollout.hip), so every path evaluates the same frame bit for bit.
-// Compiled with -ffp-contract=off (see drone_step.hip).
+// The SoA plumbing around it (typed state pointers, lane loads and stores) is
+// lane_io.h's.  Compiled with -ffp-contract=off (see rollout.hip).
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -770,25 +771,6 @@ __device__ __forceinline__ double reinforce_reward(const double v[13], uint32_t 
     return total;
 }
 
-// element i of a lane array (i < kChunk)
-template <typename E>
-__device__ __forceinline__ E& at(E* base, uint32_t i) {
-    using B = typename std::conditional<std::is_const<E>::value, const char, char>::type;
-    return *reinterpret_cast<E*>(reinterpret_cast<B*>(base) + (uint32_t)(i * (uint32_t)sizeof(E)));
-}
-
-// A wave-uniform pointer the compiler cannot prove uniform (it comes from
-// threadIdx-derived arithmetic, or is hoisted into a VGPR), moved to SGPRs so
-// loads and stores use the SGPR-base + 32-bit lane offset form and its
-// arithmetic stays on the scalar unit.
-template <typename P>
-__device__ __forceinline__ P* uniform_ptr(P* q) {
-    const uint64_t v = reinterpret_cast<uint64_t>(q);
-    const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)v);
-    const uint32_t hi = __builtin_amdgcn_readfirstlane((uint32_t)(v >> 32));
-    return reinterpret_cast<P*>(((uint64_t)hi << 32) | lo);
-}
-
 // The state between two frames is what dd_step would store: rounded to the
 // storage width T (a no-op for double).
 // Under kRef the pad is static: px / py only change on a re-spawn, to
@@ -800,29 +782,4 @@ __device__ __forceinline__ void quantize(Lane& s) {
     if constexpr (!kRef) { s.px = (T)s.px; s.py = (T)s.py; }
 }
 
-// The SoA of one batch (DDState) with typed pointers, offset to lane `first`.
-template <typename T>
-struct Soa {
-    T *x, *y, *vx, *vy, *angle, *omega, *fuel, *px, *py, *total;
-    uint8_t* status;
-    int32_t *steps, *episode;
-    int64_t env_id_base;
-};
-
-template <typename T>
-Soa<T> soa_of(const DDState& st, int64_t first) {
-    Soa<T> s;
-    s.x = (T*)st.x + first; s.y = (T*)st.y + first; s.vx = (T*)st.vx + first; s.vy = (T*)st.vy + first;
-    s.angle = (T*)st.angle + first; s.omega = (T*)st.omega + first; s.fuel = (T*)st.fuel + first;
-    s.px = (T*)st.px + first; s.py = (T*)st.py + first; s.total = (T*)st.total_reward + first;
-    s.status = st.status + first; s.steps = st.steps + first; s.episode = st.episode + first;
-    s.env_id_base = st.env_id_base + first;
-    return s;
-}
-
-inline bool state_ok(const DDState* st) {
-    return st && st->x && st->y && st->vx && st->vy && st->angle && st->omega && st->fuel && st->px &&
-           st->py && st->total_reward && st->status && st->steps && st->episode &&
-           (st->precision == DD_F32 || st->precision == DD_F64);
-}
 }  // namespace dd

@@ -3,7 +3,7 @@
 // round 6) are keyed by (seed; global env id, episode, 0), in-kernel random
 // actions (10 rounds) by
 // (seed; env id, step >> 5, 0xA5A5A5A5 ^ (step >> 5)_hi), one block per 32
-// steps (drone_step.hip rollout_action), policy samples by
+// steps (rollout.hip rollout_action), policy samples by
 // (seed; env id, step, 0x5A5A5A5A ^ step_hi) (10 rounds).  Keyed by the global env id, a
 // lane's draws do not depend on sharding or launch geometry.
 #pragma once

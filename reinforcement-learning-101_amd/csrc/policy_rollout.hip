@@ -40,6 +40,8 @@
 
 #include "dronestep.h"
 #include "frame.h"
+#include "lane_io.h"
+#include "launch.h"
 #include "mlp_core.h"
 
 namespace dd {
@@ -381,8 +383,7 @@ extern "C" int dd_policy_rollout_sampled(const DDConfig* cfg, const DDState* st,
     if (compute != DD_MLP_F32 && compute != DD_MLP_F16X3) return hipErrorInvalidValue;
     if ((io->engine_reward == nullptr) != (io->engine_done == nullptr)) return hipErrorInvalidValue;
     if (io->shaped_mode != DD_SHAPED_PPO && io->shaped_mode != DD_SHAPED_REINFORCE) return hipErrorInvalidValue;
-    const int shape = io->shaped_mode == DD_SHAPED_REINFORCE ? dd::kShapeReinforce
-                      : io->shaped_hist ? dd::kShapePpo : dd::kShapeNone;
+    const int shape = dd::shape_of(io->shaped_mode, io->shaped_hist, nullptr);
     if (io->engine_reward && shape == dd::kShapeNone) return hipErrorInvalidValue;
     if (n == 0) return hipSuccess;
     // the per-frame buffers are optional only next to the statistics

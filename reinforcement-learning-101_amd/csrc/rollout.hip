@@ -1,4 +1,7 @@
-// drone_step.hip — MI355X (gfx950) kernels behind include/dronestep.h.
+// rollout.hip — dd_rollout: `frames` consecutive frames per launch, its
+// kernel (single-role and split frame / writer) and its entry points, and the
+// device error word.  dd_step's kernels are step.hip's, the small state
+// kernels env_ops.hip's; what follows holds for all of them.
 //
 // One lane = one drone.  The frame of DroneGame.step (reference
 // delivery_drone/game/game_engine.py:95-138) is evaluated in IEEE double in
@@ -25,323 +28,12 @@
 
 #include "dronestep.h"
 #include "frame.h"
+#include "lane_io.h"
+#include "launch.h"
 #include "philox.h"
 #include "trig.h"
 
 namespace dd {
-
-constexpr int kBlock = 256;  // 4 waves; one obs tile = 256 rows
-constexpr int kWave = 64;
-// Lanes per launch: keeps every byte offset (lane x 8 B) below 2^31.
-constexpr int64_t kChunk = int64_t(1) << 28;
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
-// ---------------------------------------------------------------------------
-// SoA access: wave-uniform base pointers (SGPRs) + one 32-bit byte offset per
-// lane, so every load/store is `global_load_dword v, v_off, s[base]`.
-// ---------------------------------------------------------------------------
-
-// Store cache policies (gfx950), measured per stream: the
-// SoA state is stored plainly (write-back into the XCD's L2; the next step
-// reads it there), the output streams this kernel never re-reads (reward,
-// done, observation rows) with the non-temporal hint (+2-6 % at 262,144 and
-// 16.8M lanes).  Write-through (sc1) state stores made the next step's loads
-// miss L2 (0.5 -> 1.35 us), non-temporal state stores / loads were slower.
-template <typename E>
-__device__ __forceinline__ void store_nt(E* base, uint32_t i, E v) {
-    __builtin_nontemporal_store(v, &at(base, i));
-}
-
-typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-
-// Output streams this kernel never re-reads (reward, done) are stored
-// non-temporally, like the obs tile.
-template <typename E>
-__device__ __forceinline__ void put_out(E* base, uint32_t i, E v) {
-    asm volatile("" : "+v"(i));  // keep the offset 32-bit and local: SGPR-base store
-    store_nt(base, i, v);
-}
-
-template <typename T>
-__device__ __forceinline__ void load_dynamics(const Soa<T>& a, uint32_t i, Lane& s) {
-    s.x = at(a.x, i); s.y = at(a.y, i); s.vx = at(a.vx, i); s.vy = at(a.vy, i);
-    s.angle = at(a.angle, i); s.omega = at(a.omega, i); s.fuel = at(a.fuel, i);
-    s.px = at(a.px, i); s.py = at(a.py, i);
-}
-
-template <typename E>
-__device__ __forceinline__ void put_state(E* base, uint32_t i, E v) {
-    at(base, i) = v;
-}
-
-template <typename T>
-__device__ __forceinline__ void store_dynamics(const Soa<T>& a, uint32_t i, const Lane& s) {
-    put_state(a.x, i, (T)s.x); put_state(a.y, i, (T)s.y); put_state(a.vx, i, (T)s.vx);
-    put_state(a.vy, i, (T)s.vy); put_state(a.angle, i, (T)s.angle); put_state(a.omega, i, (T)s.omega);
-    put_state(a.fuel, i, (T)s.fuel);
-}
-
-template <typename T, bool kTotal = true>
-__device__ __forceinline__ void store_spawn(const Soa<T>& a, uint32_t i, const Lane& s) {
-    store_dynamics(a, i, s);
-    at(a.px, i) = (T)s.px; at(a.py, i) = (T)s.py;
-    if constexpr (kTotal) at(a.total, i) = (T)s.total;
-    at(a.status, i) = (uint8_t)s.status;
-    at(a.steps, i) = s.steps;
-    at(a.episode, i) = s.episode;
-}
-
-// Writes a block's [rows, 15] observation tile from LDS to global memory as
-// 16-byte stores (non-temporal: the rows are the step's output stream, read
-// by the consumer, not by this kernel again).  dst = first row of the tile.
-template <int NB = kBlock>
-__device__ __forceinline__ void flush_obs_tile(const float* tile, float* dst, int rows) {
-    const int nf = rows * DD_OBS_DIM;
-    // tiles start at multiples of 256 rows (15360 B): dst is 16-B aligned iff obs is
-    if ((reinterpret_cast<uintptr_t>(dst) & 15u) == 0) {
-        const int nv = nf >> 2;
-        const f32x4* src4 = reinterpret_cast<const f32x4*>(tile);
-        f32x4* dst4 = reinterpret_cast<f32x4*>(dst);
-        for (int k = threadIdx.x; k < nv; k += NB) __builtin_nontemporal_store(src4[k], &dst4[k]);
-        for (int k = (nv << 2) + threadIdx.x; k < nf; k += NB) dst[k] = tile[k];
-    } else {
-        for (int k = threadIdx.x; k < nf; k += NB) dst[k] = tile[k];
-    }
-}
-
-// The same for one wave's slice of the tile (rows <= 64, starting at the
-// wave's first row): only this wave wrote and reads the slice, so a
-// wave-level sync stands in for the block barrier and each wave's rows leave
-// as soon as its own lanes are done.  dst + 64-row slices of 3840 B keep
-// the 16-byte alignment of the tile.
-__device__ __forceinline__ void flush_obs_wave(const float* wtile, float* dst, int rows) {
-    __syncwarp();
-    const int lane = threadIdx.x & (kWave - 1);
-    const int nf = rows * DD_OBS_DIM;
-    if ((reinterpret_cast<uintptr_t>(dst) & 15u) == 0) {
-        const int nv = nf >> 2;
-        const f32x4* src4 = reinterpret_cast<const f32x4*>(wtile);
-        f32x4* dst4 = reinterpret_cast<f32x4*>(uniform_ptr(dst));
-        for (int k = lane; k < nv; k += kWave) store_nt(dst4, (uint32_t)k, src4[k]);
-        for (int k = (nv << 2) + lane; k < nf; k += kWave) dst[k] = wtile[k];
-    } else {
-        for (int k = lane; k < nf; k += kWave) dst[k] = wtile[k];
-    }
-    __syncwarp();  // the slice may be rewritten next (rollout frames)
-}
-
-template <int AFMT>
-__device__ __forceinline__ uint32_t load_action(const void* actions, uint32_t i) {
-    if constexpr (AFMT == DD_ACT_BITMASK) {
-        return at(static_cast<const uint8_t*>(actions), i);
-    } else if constexpr (AFMT == DD_ACT_F32X3) {
-        const float* a = &at(static_cast<const float*>(actions), 3 * i);
-        return (a[0] != 0.0f ? 1u : 0u) | (a[1] != 0.0f ? 2u : 0u) | (a[2] != 0.0f ? 4u : 0u);
-    } else {
-        const uint8_t* a = &at(static_cast<const uint8_t*>(actions), 3 * i);
-        return (a[0] ? 1u : 0u) | (a[1] ? 2u : 0u) | (a[2] ? 4u : 0u);
-    }
-}
-
-// ---------------------------------------------------------------------------
-// dd_step kernel: one 256-lane tile per block, one chunk of lanes per launch.
-// ---------------------------------------------------------------------------
-struct StepArgs {
-    Consts k;              // runtime constants (switches, spawn; physics when !kRef)
-    const void* actions;   // chunk-relative
-    void* reward;
-    uint8_t* done;
-    float* obs;
-    int32_t* done_idx;
-    int32_t* done_count;
-    int32_t n;             // lanes in this chunk
-    int32_t idx_base;      // chunk start, for done_idx entries
-    double* shaped_hist;   // slot 0 of this chunk; slot 1 at + hist_stride
-    int64_t hist_stride;
-    void* shaped_reward;
-    uint8_t* shaped_done;
-    int32_t max_steps;
-};
-
-// 256 lanes per block: 128 / 512 / 1024 measured +0 / +4 / +14 % at 262,144
-// drones; no occupancy floor (forcing 8 waves per SIMD spilled).
-constexpr int kStepBlock = 256;
-
-// A lane's inputs as loaded (storage width), before widening to double.
-template <typename T>
-struct Raw {
-    T x, y, vx, vy, angle, omega, fuel, px, py, total;
-    uint32_t status, act;
-    int32_t steps;
-};
-
-template <typename T, int AFMT>
-__device__ __forceinline__ void load_raw(const Soa<T>& a, const void* actions, uint32_t i, Raw<T>& r) {
-    // The action is loaded first and pinned below: only the live branch reads
-    // it, and left to itself the compiler sank its load into that branch,
-    // i.e. behind the wait for the status byte: a second memory round trip.
-    r.act = load_action<AFMT>(actions, i);
-    r.x = at(a.x, i); r.y = at(a.y, i); r.vx = at(a.vx, i); r.vy = at(a.vy, i);
-    r.angle = at(a.angle, i); r.omega = at(a.omega, i); r.fuel = at(a.fuel, i);
-    r.px = at(a.px, i); r.py = at(a.py, i); r.total = at(a.total, i);
-    r.status = at(a.status, i);
-    r.steps = at(a.steps, i);
-    asm volatile("" ::"v"(r.act));  // every load is issued; this waits for the oldest only
-}
-
-// Everything after the loads for one lane: the frame (or sticky done / auto
-// reset), the state and output stores, the observation row into `orow`
-// (LDS).  Returns whether the lane's episode ended in this call.  The fast
-// frame may report the lane risky (frame.h): then, in a wave-uniform rare
-// branch, the lane's frame is redone at once from its loaded inputs with
-// kExact (glibc's sin, cos and pow), and the rest of the lane's work is
-// shared.  (Until round 6 a second finish_lane pass over the risky lanes
-// redid everything after the loads: the same results, but that copy of the
-// observation, reward and store code cost config 3 1-2 % in time and ~110
-// instruction-wait cycles per wave, profiles/r06/lab/step_inline_exact.jsonl.)
-// kShape: the notebooks' reward fused (frame.h, kShapePpo / kShapeReinforce).
-// kPP (ping-pong, DDStepIO.state_out): the nine per-frame fields (x y vx vy
-// angle omega fuel total steps) go to `o`; px, py, status and episode always
-// go to `a`.  In place (the usual case) the kernel has no `o` at all.
-template <typename T, bool kRef, int kShape, bool kPP>
-__device__ __forceinline__ bool finish_lane(const StepArgs& p, const Soa<T>& a, const Soa<T>& o, uint32_t i,
-                                            const Raw<T>& r, float* orow) {
-    const DDConfig& sw = p.k.c;
-    const Consts& k = kRef ? kRefConsts : p.k;
-    Lane s;
-    s.x = r.x; s.y = r.y; s.vx = r.vx; s.vy = r.vy; s.angle = r.angle; s.omega = r.omega;
-    s.fuel = r.fuel; s.px = r.px; s.py = r.py; s.total = r.total;
-    s.status = r.status;
-    s.steps = r.steps;
-    bool ended = false;
-    bool respawned = false;
-    double reward;
-    double shaped = 0.0;
-    bool shaped_done = false;
-    if (s.status & DD_ST_DONE) {
-        reward = 0.0;
-        if (sw.auto_reset) {  // next-step reset: fresh episode, reward 0, done 0
-            s.episode = at(a.episode, i);
-            spawn(sw, k.c.max_fuel, a.env_id_base + i, s);
-            respawned = true;
-            if constexpr (kShape == kShapePpo) {  // the notebook's history restarts: prev_state None
-                at(p.shaped_hist, i) = trig::div_exact(s.dist, k.c.world_width, k.inv_w);
-                at(p.shaped_hist + p.hist_stride, i) = __builtin_nan("");
-            }
-        } else {  // sticky done (game_engine.py:107-111): nothing changes
-            measure(s);
-            shaped_done = true;
-        }
-    } else {
-        bool rk = false;
-        reward = frame<kRef, false>(k, sw, r.act, s, &rk);
-        if (__builtin_expect(__ballot(rk) != 0, 0)) {
-            if (rk) {  // the frame again from the loaded state, the reference's functions (frame.h)
-                s.x = r.x; s.y = r.y; s.vx = r.vx; s.vy = r.vy; s.angle = r.angle; s.omega = r.omega;
-                s.fuel = r.fuel; s.px = r.px; s.py = r.py; s.total = r.total; s.status = r.status;
-                s.steps = r.steps;
-                reward = frame<kRef, false, true>(k, sw, r.act, s, nullptr);
-            }
-        }
-        if constexpr (kShape != kShapeNone) {
-            double v[13];
-            observe_values<false, true>(k, s, v);  // the notebook reward's doubles: exact quotients
-            if constexpr (kShape == kShapePpo) {
-                double* slot = p.shaped_hist + (s.steps & 1) * p.hist_stride;  // two frames back
-                shaped = notebook_reward(v, s.status, at(slot, i));
-                at(slot, i) = v[9];
-            } else {
-                shaped = reinforce_reward(v, s.status);
-            }
-            shaped_done = (s.status & DD_ST_DONE) != 0;
-            if (p.max_steps > 0 && s.steps >= p.max_steps) {  // the collection loops' timeout
-                shaped = (s.status & DD_ST_LANDED) ? shaped : shaped - 500;
-                shaped_done = true;
-                s.status |= DD_ST_DONE;  // the episode ends here (TimeLimit)
-            }
-            if (p.obs) observe(k, s, orow);  // rows as every other path writes them
-        }
-        ended = (s.status & DD_ST_DONE) != 0;
-    }
-    // State stores after the branches merge, so each is one SGPR-base +
-    // lane-offset store (stores inside the branches got 64-bit per-lane
-    // addresses, 22 VGPRs live across the frame).  A sticky-done lane
-    // writes nothing; status and px only change on the terminal frame, a
-    // respawn or a moving platform; py and episode only on a respawn.
-    // (with separate out arrays a sticky lane copies its fields across)
-    const bool sticky = (r.status & DD_ST_DONE) && !respawned && !kPP;
-    if (!sticky) {
-        uint32_t j = i;
-        asm volatile("" : "+v"(j));  // an offset defined in this block: isel folds it into saddr stores
-        store_dynamics(o, j, s);
-        put_state(o.steps, j, s.steps);
-        put_state(o.total, j, (T)s.total);
-        const bool moving = !kRef && sw.platform_moving;
-        if (moving || respawned) put_state(a.px, j, (T)s.px);
-        if (moving || ended || respawned) put_state(a.status, j, (uint8_t)s.status);
-        if (respawned) { put_state(a.py, j, (T)s.py); put_state(a.episode, j, s.episode); }
-    }
-    put_out(static_cast<T*>(p.reward), i, (T)reward);
-    put_out(p.done, i, (uint8_t)((s.status & DD_ST_DONE) ? 1 : 0));
-    if constexpr (kShape != kShapeNone) {
-        put_out(static_cast<T*>(p.shaped_reward), i, (T)shaped);
-        put_out(p.shaped_done, i, (uint8_t)(shaped_done ? 1 : 0));
-        if (p.obs && ((r.status & DD_ST_DONE) != 0)) observe(k, s, orow);  // the live path wrote its row
-    } else {
-        if (p.obs) observe(k, s, orow);
-    }
-    return ended;
-}
-
-// One step tile: one drone per lane, kStepBlock lanes.  `o` is `a` unless kPP.
-template <typename T, int AFMT, bool kRef, int kShape, bool kPP>
-__device__ __forceinline__ void step_tile(const StepArgs& p, const Soa<T>& a, const Soa<T>& o) {
-    __shared__ __attribute__((aligned(16))) float tile[kStepBlock * DD_OBS_DIM];
-    const uint32_t row0 = blockIdx.x * kStepBlock;
-    const uint32_t i = row0 + threadIdx.x;
-    // The load bases are wanted in SGPRs before the lane test: left to
-    // itself the compiler sank their kernarg loads into the `i < n` branch,
-    // one scalar-load latency later than the state loads could start.
-    asm volatile("" ::"s"(a.x), "s"(a.y), "s"(a.vx), "s"(a.vy), "s"(a.angle), "s"(a.omega), "s"(a.fuel),
-                 "s"(a.px), "s"(a.py), "s"(a.total), "s"(a.status), "s"(a.steps), "s"(p.actions));
-    Raw<T> r;
-    if (i < (uint32_t)p.n) load_raw<T, AFMT>(a, p.actions, i, r);
-    const bool ended = i < (uint32_t)p.n &&
-                       finish_lane<T, kRef, kShape, kPP>(p, a, o, i, r, tile + threadIdx.x * DD_OBS_DIM);
-    if (p.done_idx) {  // wave-ballot compaction of the lanes that just ended
-        const uint64_t m = __ballot(ended);
-        if (m) {
-            const int lane = threadIdx.x & (kWave - 1);
-            const int leader = __ffsll((unsigned long long)m) - 1;
-            const int before = __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32),
-                                                         __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0));
-            int b = 0;
-            if (lane == leader) b = atomicAdd(p.done_count, __popcll(m));
-            b = __shfl(b, leader);
-            if (ended) p.done_idx[b + before] = p.idx_base + (int32_t)i;
-        }
-    }
-    if (p.obs) {  // each wave's 64 rows leave as 16-byte stores
-        const uint32_t wrow0 = row0 + (threadIdx.x & ~(kWave - 1));
-        const int rows = (int)min((int64_t)kWave, max((int64_t)0, (int64_t)p.n - wrow0));
-        flush_obs_wave(tile + (threadIdx.x & ~(kWave - 1)) * DD_OBS_DIM, p.obs + (size_t)wrow0 * DD_OBS_DIM, rows);
-    }
-}
-
-// dd_step kernel, in place (the usual case: one set of state bases).
-template <typename T, int AFMT, bool kRef, int kShape>
-__global__ __launch_bounds__(kStepBlock) void step_kernel(StepArgs p, Soa<T> a) {
-    step_tile<T, AFMT, kRef, kShape, false>(p, a, a);
-}
-
-// dd_step kernel with ping-pong state (DDStepIO.state_out): its own
-// instantiation, so the in-place kernel carries none of its plumbing (the
-// shared kernel's `if (!ping_pong) o = a` had cost config 3 ~0.1 us).
-template <typename T, int AFMT, bool kRef, int kShape>
-__global__ __launch_bounds__(kStepBlock) void step_pp_kernel(StepArgs p, Soa<T> a, Soa<T> o) {
-    step_tile<T, AFMT, kRef, kShape, true>(p, a, o);
-}
 
 // ---------------------------------------------------------------------------
 // dd_rollout kernel: `frames` consecutive frames per launch, the lane's state
@@ -721,7 +413,7 @@ __global__ __launch_bounds__(kSplit ? 2 * kBlock : kBlock, kRollMinWaves) void r
     // v_and 0xffff) the compiler placed at the loop latch, right behind the
     // pair's stores, and waited there for the load.
     constexpr bool kActDw = kHeld && AFMT == DD_ACT_BITMASK;
-    constexpr uint32_t act_w = AFMT == DD_ACT_F32X3 ? 12u : AFMT == DD_ACT_U8X3 ? 3u : 1u;
+    constexpr uint32_t act_w = (uint32_t)action_bytes(AFMT);
     const __amdgpu_buffer_rsrc_t act_r = rsrc_over(p.actions, AFMT == DD_ACT_PHILOX ? 0u : p.act_bytes);
     const uint32_t act_lane = kActDw ? (i & ~3u) : i * act_w;
     const uint32_t act_sh = (i & 3u) * 8u;
@@ -910,230 +602,6 @@ __global__ __launch_bounds__(kSplit ? 2 * kBlock : kBlock, kRollMinWaves) void r
     }
 }
 
-// dd_selftest_sqrt kernel: trig::sqrt_unscaled against the compiler's sqrt()
-// on doubles from 2^-767 up, drawn with a uniform exponent (Philox bits: 11
-// exponent bits folded into [255, 2047), 52 random mantissa bits), plus the
-// integers 0..2^20 (spawn distances) at the start of the range; counts the
-// inputs whose results differ in any bit.
-__global__ __launch_bounds__(kBlock) void sqrt_selftest_kernel(uint64_t seed, uint64_t first, int64_t len,
-                                                               unsigned long long* mismatches) {
-    const uint64_t t = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
-    uint32_t r[4];
-    philox4x32_10((uint32_t)(first + 4 * t), (uint32_t)((first + 4 * t) >> 32), 0x5a17u, 0u, (uint32_t)seed,
-                  (uint32_t)(seed >> 32), r);
-    int bad = 0;
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-        const uint64_t idx = 4 * t + q;
-        if ((int64_t)idx >= len) break;
-        const uint64_t g = first + idx;
-        double x;
-        if (g <= (1u << 20)) {
-            x = (double)g;
-        } else {
-            const uint32_t hi = r[q], lo = r[(q + 1) & 3] ^ r[(q + 2) & 3];
-            const uint64_t exp = 256u + (hi >> 21) % 1791u;  // [256, 2047): 2^-767 .. below inf
-            const uint64_t mant = ((uint64_t)(hi & 0xfffffu) << 32) | lo;
-            x = __builtin_bit_cast(double, (exp << 52) | mant);
-        }
-        const double a = sqrt(x), b = trig::sqrt_unscaled(x);
-        bad += __builtin_bit_cast(uint64_t, a) != __builtin_bit_cast(uint64_t, b);
-    }
-    const uint64_t m = __ballot(bad != 0);
-    if (m) {
-        int total = bad;
-        for (int off = 32; off > 0; off >>= 1) total += __shfl_xor(total, off);
-        if ((threadIdx.x & (kWave - 1)) == __ffsll((unsigned long long)m) - 1) atomicAdd(mismatches, (unsigned long long)total);
-    }
-}
-
-// dd_stamp kernel: one lane stores the GPU's constant-rate wall clock
-// (s_memrealtime) with a vector store.  Captured into a hipGraph beside the
-// step kernels it marks where the graph reaches that point (bench.py).
-__global__ __launch_bounds__(kWave) void stamp_kernel(unsigned long long* slot) {
-    const unsigned long long t = (unsigned long long)wall_clock64();
-    if (threadIdx.x == 0) *slot = t;
-}
-
-// dd_shaped_reset kernel: the notebook reward's history restarts from the
-// current state (slot 0 = its distance, slot 1 = none).
-template <typename T>
-__global__ __launch_bounds__(kBlock) void shaped_reset_kernel(Consts k, Soa<T> a, const uint8_t* mask,
-                                                              double* hist, int64_t stride, int32_t n) {
-    const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
-    if (i >= (uint32_t)n) return;
-    if (mask && !at(mask, i)) return;
-    Lane s;
-    load_dynamics(a, i, s);
-    measure(s);
-    at(hist, i) = trig::div_exact(s.dist, k.c.world_width, k.inv_w);
-    at(hist + stride, i) = __builtin_nan("");
-}
-
-// dd_reset kernel: masked re-spawn (+ optional reset observation).
-template <typename T>
-__global__ __launch_bounds__(kBlock) void reset_kernel(Consts k, Soa<T> a, const uint8_t* mask,
-                                                       float* obs, int32_t n) {
-    const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
-    if (i >= (uint32_t)n) return;
-    if (mask && !at(mask, i)) return;
-    Lane s;
-    s.episode = at(a.episode, i);
-    spawn(k.c, k.c.max_fuel, a.env_id_base + i, s);
-    store_spawn(a, i, s);
-    if (obs) observe(k, s, obs + (size_t)i * DD_OBS_DIM);
-}
-
-// dd_write_obs kernel: observation of the current state, LDS-staged.
-template <typename T>
-__global__ __launch_bounds__(kBlock) void obs_kernel(Consts k, Soa<T> a, float* obs, int32_t n) {
-    __shared__ __attribute__((aligned(16))) float tile[kBlock * DD_OBS_DIM];
-    const uint32_t row0 = blockIdx.x * kBlock;
-    const uint32_t i = row0 + threadIdx.x;
-    if (i < (uint32_t)n) {
-        Lane s;
-        load_dynamics(a, i, s);
-        s.status = at(a.status, i);
-        measure(s);
-        observe(k, s, tile + threadIdx.x * DD_OBS_DIM);
-    }
-    __syncthreads();
-    const int rows = (int)min((uint32_t)kBlock, (uint32_t)n - row0);
-    flush_obs_tile(tile, obs + (size_t)row0 * DD_OBS_DIM, rows);
-}
-
-// dd_get_info kernel: pixel distance and speed (game_engine.py:292-296).
-template <typename T>
-__global__ __launch_bounds__(kBlock) void info_kernel(Soa<T> a, T* distance, T* speed, int32_t n) {
-    const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
-    if (i >= (uint32_t)n) return;
-    const double x = at(a.x, i), y = at(a.y, i), vx = at(a.vx, i), vy = at(a.vy, i);
-    const double dx = (double)at(a.px, i) - x, dy = (double)at(a.py, i) - y;
-    if (distance) at(distance, i) = (T)sqrt(dx * dx + dy * dy);
-    if (speed) at(speed, i) = (T)sqrt(vx * vx + vy * vy);
-}
-
-// ---------------------------------------------------------------------------
-// dd_gae: one lane per env walks its column of the [T][N] rollout backwards.
-// The loads of a frame do not depend on the running gae, so the compiler
-// keeps several frames' loads in flight (unroll 4).  Float32 throughout, in
-// compute_gae's order: torch evaluates `gamma * v` with gamma rounded to
-// float32 and `gamma * lambda_` in Python doubles before that rounding.
-// ---------------------------------------------------------------------------
-__global__ __launch_bounds__(kBlock) void gae_kernel(const float* __restrict__ rewards,
-                                                     const float* __restrict__ values,
-                                                     const uint8_t* __restrict__ dones, float* __restrict__ adv,
-                                                     float* __restrict__ ret, int32_t T, int64_t n, float g,
-                                                     float gl) {
-    // Frames are processed in groups of kG: the group's loads are all issued
-    // before its (serial) arithmetic, so kG loads per array are in flight.
-    constexpr int kG = 8;
-    const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
-    if (i >= n) return;
-    float gae = 0.0f;
-    float v_next = values[(int64_t)T * n + i];
-    int32_t t = T - 1;
-    for (; t >= kG - 1; t -= kG) {
-        float r[kG], v[kG], d[kG];
-#pragma unroll
-        for (int j = 0; j < kG; ++j) {
-            const int64_t o = (int64_t)(t - j) * n + i;
-            r[j] = rewards[o];
-            v[j] = values[o];
-            d[j] = (float)dones[o];
-        }
-#pragma unroll
-        for (int j = 0; j < kG; ++j) {
-            const int64_t o = (int64_t)(t - j) * n + i;
-            const float mask = 1.0f - d[j];
-            const float delta = (r[j] + (g * v_next) * mask) - v[j];
-            gae = delta + (gl * mask) * gae;
-            __builtin_nontemporal_store(gae, adv + o);
-            if (ret) __builtin_nontemporal_store(gae + v[j], ret + o);
-            v_next = v[j];
-        }
-    }
-    for (; t >= 0; --t) {
-        const int64_t o = (int64_t)t * n + i;
-        const float v = values[o];
-        const float mask = 1.0f - (float)dones[o];
-        const float delta = (rewards[o] + (g * v_next) * mask) - v;
-        gae = delta + (gl * mask) * gae;
-        __builtin_nontemporal_store(gae, adv + o);
-        if (ret) __builtin_nontemporal_store(gae + v, ret + o);
-        v_next = v;
-    }
-}
-
-// ---------------------------------------------------------------------------
-// Ordered compaction (dd_compact): count per tile -> exclusive scan of tile
-// counts -> scatter in lane order.  Ballots give each wave its count and each
-// lane its rank; LDS combines the block's four waves.
-// ---------------------------------------------------------------------------
-__device__ __forceinline__ bool want_flag(const uint8_t* flags, int32_t want, int64_t i, int64_t n) {
-    return i < n && ((flags[i] != 0) == (want != 0));
-}
-
-__global__ __launch_bounds__(kBlock) void compact_count_kernel(const uint8_t* flags, int32_t want,
-                                                               int32_t* tile_counts, int64_t n) {
-    __shared__ int wave_cnt[kBlock / kWave];
-    const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
-    const uint64_t m = __ballot(want_flag(flags, want, i, n));
-    if ((threadIdx.x & (kWave - 1)) == 0) wave_cnt[threadIdx.x / kWave] = __popcll(m);
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        int sum = 0;
-        for (int w = 0; w < kBlock / kWave; ++w) sum += wave_cnt[w];
-        tile_counts[blockIdx.x] = sum;
-    }
-}
-
-// Single-block exclusive scan over `m` tile counts; total goes to *count.
-__global__ __launch_bounds__(1024) void compact_scan_kernel(int32_t* tile_counts, int64_t m, int32_t* count) {
-    __shared__ int32_t part[1024];
-    __shared__ int32_t carry;
-    if (threadIdx.x == 0) carry = 0;
-    __syncthreads();
-    for (int64_t base = 0; base < m; base += 1024) {
-        const int64_t j = base + threadIdx.x;
-        const int32_t v = j < m ? tile_counts[j] : 0;
-        part[threadIdx.x] = v;
-        __syncthreads();
-        for (int off = 1; off < 1024; off <<= 1) {  // Hillis-Steele inclusive scan
-            const int32_t add = threadIdx.x >= (unsigned)off ? part[threadIdx.x - off] : 0;
-            __syncthreads();
-            part[threadIdx.x] += add;
-            __syncthreads();
-        }
-        if (j < m) tile_counts[j] = carry + part[threadIdx.x] - v;
-        __syncthreads();
-        if (threadIdx.x == 1023) carry += part[1023];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) *count = carry;
-}
-
-__global__ __launch_bounds__(kBlock) void compact_scatter_kernel(const uint8_t* flags, int32_t want,
-                                                                 const int32_t* tile_offsets,
-                                                                 int32_t* idx_out, int64_t n) {
-    __shared__ int wave_off[kBlock / kWave];
-    const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
-    const bool keep = want_flag(flags, want, i, n);
-    const uint64_t m = __ballot(keep);
-    const int w = threadIdx.x / kWave;
-    if ((threadIdx.x & (kWave - 1)) == 0) wave_off[w] = __popcll(m);
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        int run = tile_offsets[blockIdx.x];
-        for (int k = 0; k < kBlock / kWave; ++k) { const int c = wave_off[k]; wave_off[k] = run; run += c; }
-    }
-    __syncthreads();
-    if (keep) {
-        const int rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0));
-        idx_out[wave_off[w] + rank] = (int32_t)i;
-    }
-}
-
 #ifdef DD_ISA_PROBE
 // tools/lab/isa_probe.sh: one kernel instantiation alone (device assembly in
 // seconds instead of the whole library's minutes), for reading its ISA.
@@ -1144,68 +612,6 @@ DD_PROBE_KERNEL_(DD_ISA_PROBE)
 // ---------------------------------------------------------------------------
 // Host side: argument checks, chunking and launches.
 // ---------------------------------------------------------------------------
-inline int64_t tiles_of(int64_t n) { return (n + kBlock - 1) / kBlock; }
-
-// The notebook reward a call asks for (frame.h kShape*): REINFORCE's by its
-// mode, PPO's when the history pointer is set, else none.
-inline int shape_of(int32_t shaped_mode, const void* shaped_hist, const void* shaped_reward) {
-    if (shaped_mode == DD_SHAPED_REINFORCE) return kShapeReinforce;
-    return shaped_hist || shaped_reward ? kShapePpo : kShapeNone;
-}
-
-template <typename T, int AFMT, bool kRef, int kShape>
-void launch_step(const StepArgs& p, const Soa<T>& a, const Soa<T>* o, hipStream_t s) {
-    const unsigned blocks = (unsigned)((p.n + kStepBlock - 1) / kStepBlock);
-    if (o)
-        hipLaunchKernelGGL((step_pp_kernel<T, AFMT, kRef, kShape>), dim3(blocks), dim3(kStepBlock), 0, s, p, a, *o);
-    else
-        hipLaunchKernelGGL((step_kernel<T, AFMT, kRef, kShape>), dim3(blocks), dim3(kStepBlock), 0, s, p, a);
-}
-
-template <typename T, bool kRef, int kShape>
-void launch_step_fmt(const StepArgs& p, int afmt, const Soa<T>& a, const Soa<T>* o, hipStream_t s) {
-    switch (afmt) {
-        case DD_ACT_BITMASK: launch_step<T, DD_ACT_BITMASK, kRef, kShape>(p, a, o, s); break;
-        case DD_ACT_F32X3: launch_step<T, DD_ACT_F32X3, kRef, kShape>(p, a, o, s); break;
-        default: launch_step<T, DD_ACT_U8X3, kRef, kShape>(p, a, o, s); break;
-    }
-}
-
-template <typename T, bool kRef>
-void launch_step_shape(const StepArgs& p, int shape, int afmt, const Soa<T>& a, const Soa<T>* o, hipStream_t s) {
-    switch (shape) {
-        case kShapeNone: launch_step_fmt<T, kRef, kShapeNone>(p, afmt, a, o, s); break;
-        case kShapePpo: launch_step_fmt<T, kRef, kShapePpo>(p, afmt, a, o, s); break;
-        default: launch_step_fmt<T, kRef, kShapeReinforce>(p, afmt, a, o, s); break;
-    }
-}
-
-template <typename T>
-void step_chunks(StepArgs p, const DDState& st, const DDStepIO& io, int64_t n, hipStream_t s) {
-    const bool ref = uses_reference_physics(p.k.c);
-    const int shape = shape_of(io.shaped_mode, io.shaped_hist, io.shaped_reward);
-    const int64_t act_w = io.action_format == DD_ACT_F32X3 ? 12 : io.action_format == DD_ACT_U8X3 ? 3 : 1;
-    for (int64_t first = 0; first < n; first += kChunk) {
-        const int64_t len = n - first < kChunk ? n - first : kChunk;
-        p.actions = static_cast<const char*>(io.actions) + first * act_w;
-        p.reward = static_cast<T*>(io.reward) + first;
-        p.done = io.done + first;
-        p.obs = io.obs ? io.obs + first * DD_OBS_DIM : nullptr;
-        p.n = (int32_t)len;
-        p.idx_base = (int32_t)first;
-        p.shaped_hist = shape == kShapePpo ? io.shaped_hist + first : nullptr;
-        p.hist_stride = n;
-        p.shaped_reward = shape != kShapeNone ? static_cast<void*>(static_cast<T*>(io.shaped_reward) + first) : nullptr;
-        p.shaped_done = shape != kShapeNone ? io.shaped_done + first : nullptr;
-        p.max_steps = io.max_steps;
-        const Soa<T> a = soa_of<T>(st, first);
-        Soa<T> o;
-        if (io.state_out) o = soa_of<T>(*io.state_out, first);
-        if (ref) launch_step_shape<T, true>(p, shape, io.action_format, a, io.state_out ? &o : nullptr, s);
-        else launch_step_shape<T, false>(p, shape, io.action_format, a, io.state_out ? &o : nullptr, s);
-    }
-}
-
 // The split rollout (rollout_kernel's kSplit) when the launch is one block per
 // CU or fewer: its block takes 8 waves of ~256 registers, all of a CU's
 // register file for 256 drones, where the single-role kernel fits two blocks
@@ -1272,16 +678,14 @@ template <typename T>
 void rollout_chunks(RolloutArgs p, const DDState& st, const DDRolloutIO& io, int64_t n, hipStream_t s) {
     const bool ref = uses_reference_physics(p.k.c);
     const int shape = shape_of(io.shaped_mode, io.shaped_hist, nullptr);
-    const int64_t act_w = io.action_format == DD_ACT_F32X3 ? 12 : io.action_format == DD_ACT_U8X3 ? 3
-                        : io.action_format == DD_ACT_BITMASK ? 1 : 0;
+    const int64_t act_w = action_bytes(io.action_format);
     p.act_stride = n * act_w;
     p.reward_stride = n * (int64_t)sizeof(T);
     p.n_total = n;
     p.spin_cap = io.kernel == DD_ROLLOUT_SPLIT_NO_WAIT ? 0 : kSpinCap;
     const int32_t frames = p.frames;
     const int64_t step0 = p.action_step;
-    for (int64_t first = 0; first < n; first += kChunk) {
-        const int64_t len = n - first < kChunk ? n - first : kChunk;
+    for_each_chunk(n, [&](int64_t first, int64_t len) {
         // The kernel reads actions by raw buffer loads with 32-bit offsets
         // (buffer_action): a launch covers as many frames as keep every
         // consumed offset, (frames - 1) x stride + len x width, below 2^32,
@@ -1312,58 +716,12 @@ void rollout_chunks(RolloutArgs p, const DDState& st, const DDRolloutIO& io, int
             if (ref) launch_rollout_shape<T, true>(p, kind, shape, io.action_format, a, s);
             else launch_rollout_shape<T, false>(p, kind, shape, io.action_format, a, s);
         }
-    }
+    });
 }
-
-int finish() { return (int)hipGetLastError(); }
 
 }  // namespace dd
 
 extern "C" {
-
-void dd_config_default(DDConfig* c) {
-    if (c) *c = dd::reference_config();
-}
-
-int dd_step(const DDConfig* cfg, const DDState* st, const DDStepIO* io, int64_t n, void* stream) {
-    if (!cfg || !io || !st || n < 0 || n > INT32_MAX) return hipErrorInvalidValue;
-    if (io->action_format < DD_ACT_BITMASK || io->action_format > DD_ACT_U8X3) return hipErrorInvalidValue;
-    if (st->precision != DD_F32 && st->precision != DD_F64) return hipErrorInvalidValue;
-    if (io->done_idx && !io->done_count) return hipErrorInvalidValue;
-    if (io->shaped_mode == DD_SHAPED_REINFORCE) {  // no history: shaped_hist is not read
-        if (!io->shaped_reward || !io->shaped_done) return hipErrorInvalidValue;
-    } else if (io->shaped_mode == DD_SHAPED_PPO) {
-        const int ptrs = (io->shaped_hist != nullptr) + (io->shaped_reward != nullptr) + (io->shaped_done != nullptr);
-        if (ptrs != 0 && ptrs != 3) return hipErrorInvalidValue;
-    } else {
-        return hipErrorInvalidValue;
-    }
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    if (io->done_count) {
-        const hipError_t e = hipMemsetAsync(io->done_count, 0, sizeof(int32_t), s);
-        if (e != hipSuccess) return (int)e;
-    }
-    if (n == 0) return 0;  // empty batch: pointers may be null
-    if (!dd::state_ok(st) || !io->actions || !io->reward || !io->done) return hipErrorInvalidValue;
-    if (const DDState* so = io->state_out) {  // ping-pong: the shared fields, distinct per-frame arrays
-        if (!dd::state_ok(so) || so->precision != st->precision || so->env_id_base != st->env_id_base ||
-            so->px != st->px || so->py != st->py || so->status != st->status || so->episode != st->episode)
-            return hipErrorInvalidValue;
-        const void* in[9] = {st->x, st->y, st->vx, st->vy, st->angle, st->omega, st->fuel, st->total_reward,
-                             st->steps};
-        const void* out[9] = {so->x, so->y, so->vx, so->vy, so->angle, so->omega, so->fuel, so->total_reward,
-                              so->steps};
-        for (int q = 0; q < 9; ++q)
-            if (in[q] == out[q]) return hipErrorInvalidValue;
-    }
-    dd::StepArgs p{};
-    p.k = dd::make_consts(*cfg);
-    p.done_idx = io->done_idx;
-    p.done_count = io->done_count;
-    if (st->precision == DD_F32) dd::step_chunks<float>(p, *st, *io, n, s);
-    else dd::step_chunks<double>(p, *st, *io, n, s);
-    return dd::finish();
-}
 
 int dd_rollout(const DDConfig* cfg, const DDState* st, const DDRolloutIO* io, int64_t n, void* stream) {
     if (!cfg || !io || !st || n < 0 || n > INT32_MAX || io->frames < 0) return hipErrorInvalidValue;
@@ -1383,8 +741,7 @@ int dd_rollout(const DDConfig* cfg, const DDState* st, const DDRolloutIO* io, in
     p.frames = io->frames;
     p.action_seed = io->action_seed;
     p.action_step = io->action_step;
-    if (st->precision == DD_F32) dd::rollout_chunks<float>(p, *st, *io, n, s);
-    else dd::rollout_chunks<double>(p, *st, *io, n, s);
+    dd::with_storage(st->precision, [&](auto tag) { dd::rollout_chunks<decltype(tag)>(p, *st, *io, n, s); });
     return dd::finish();
 }
 
@@ -1409,156 +766,6 @@ int dd_device_errors(uint32_t* bits, int32_t clear) {
     }
     return (int)e;
 }
-
-int dd_reset(const DDConfig* cfg, const DDState* st, const uint8_t* mask, float* obs, int64_t n, void* stream) {
-    if (!cfg || !st || n < 0 || n > INT32_MAX) return hipErrorInvalidValue;
-    if (n == 0) return 0;
-    if (!dd::state_ok(st)) return hipErrorInvalidValue;
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    const dd::Consts k = dd::make_consts(*cfg);
-    for (int64_t first = 0; first < n; first += dd::kChunk) {
-        const int32_t len = (int32_t)(n - first < dd::kChunk ? n - first : dd::kChunk);
-        const dim3 g((unsigned)dd::tiles_of(len)), b(dd::kBlock);
-        const uint8_t* m = mask ? mask + first : nullptr;
-        float* o = obs ? obs + first * DD_OBS_DIM : nullptr;
-        if (st->precision == DD_F32)
-            hipLaunchKernelGGL(dd::reset_kernel<float>, g, b, 0, s, k, dd::soa_of<float>(*st, first), m, o, len);
-        else
-            hipLaunchKernelGGL(dd::reset_kernel<double>, g, b, 0, s, k, dd::soa_of<double>(*st, first), m, o, len);
-    }
-    return dd::finish();
-}
-
-int dd_shaped_reset(const DDConfig* cfg, const DDState* st, const uint8_t* mask, double* hist, int64_t n,
-                    void* stream) {
-    if (!cfg || !st || n < 0 || n > INT32_MAX) return hipErrorInvalidValue;
-    if (n == 0) return 0;
-    if (!hist || !dd::state_ok(st)) return hipErrorInvalidValue;
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    const dd::Consts k = dd::make_consts(*cfg);
-    for (int64_t first = 0; first < n; first += dd::kChunk) {
-        const int32_t len = (int32_t)(n - first < dd::kChunk ? n - first : dd::kChunk);
-        const dim3 g((unsigned)dd::tiles_of(len)), b(dd::kBlock);
-        const uint8_t* m = mask ? mask + first : nullptr;
-        if (st->precision == DD_F32)
-            hipLaunchKernelGGL(dd::shaped_reset_kernel<float>, g, b, 0, s, k, dd::soa_of<float>(*st, first), m,
-                               hist + first, n, len);
-        else
-            hipLaunchKernelGGL(dd::shaped_reset_kernel<double>, g, b, 0, s, k, dd::soa_of<double>(*st, first), m,
-                               hist + first, n, len);
-    }
-    return dd::finish();
-}
-
-int dd_write_obs(const DDConfig* cfg, const DDState* st, float* obs, int64_t n, void* stream) {
-    if (!cfg || !st || n < 0 || n > INT32_MAX) return hipErrorInvalidValue;
-    if (n == 0) return 0;
-    if (!obs || !dd::state_ok(st)) return hipErrorInvalidValue;
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    const dd::Consts k = dd::make_consts(*cfg);
-    for (int64_t first = 0; first < n; first += dd::kChunk) {
-        const int32_t len = (int32_t)(n - first < dd::kChunk ? n - first : dd::kChunk);
-        const dim3 g((unsigned)dd::tiles_of(len)), b(dd::kBlock);
-        float* o = obs + first * DD_OBS_DIM;
-        if (st->precision == DD_F32)
-            hipLaunchKernelGGL(dd::obs_kernel<float>, g, b, 0, s, k, dd::soa_of<float>(*st, first), o, len);
-        else
-            hipLaunchKernelGGL(dd::obs_kernel<double>, g, b, 0, s, k, dd::soa_of<double>(*st, first), o, len);
-    }
-    return dd::finish();
-}
-
-int dd_get_info(const DDConfig* cfg, const DDState* st, void* distance, void* speed, int64_t n, void* stream) {
-    if (!cfg || !st || n < 0 || n > INT32_MAX) return hipErrorInvalidValue;
-    if (n == 0 || (!distance && !speed)) return 0;
-    if (!dd::state_ok(st)) return hipErrorInvalidValue;
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    for (int64_t first = 0; first < n; first += dd::kChunk) {
-        const int32_t len = (int32_t)(n - first < dd::kChunk ? n - first : dd::kChunk);
-        const dim3 g((unsigned)dd::tiles_of(len)), b(dd::kBlock);
-        if (st->precision == DD_F32)
-            hipLaunchKernelGGL(dd::info_kernel<float>, g, b, 0, s, dd::soa_of<float>(*st, first),
-                               distance ? (float*)distance + first : nullptr,
-                               speed ? (float*)speed + first : nullptr, len);
-        else
-            hipLaunchKernelGGL(dd::info_kernel<double>, g, b, 0, s, dd::soa_of<double>(*st, first),
-                               distance ? (double*)distance + first : nullptr,
-                               speed ? (double*)speed + first : nullptr, len);
-    }
-    return dd::finish();
-}
-
-int dd_gae(const float* rewards, const float* values, const uint8_t* dones, float* advantages, float* returns,
-           int64_t T, int64_t n, double gamma, double lambda, void* stream) {
-    if (T < 0 || n < 0 || T > INT32_MAX) return hipErrorInvalidValue;
-    if (T == 0 || n == 0) return 0;
-    if (!rewards || !values || !dones || !advantages) return hipErrorInvalidValue;
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    const float g = (float)gamma;
-    const float gl = (float)(gamma * lambda);
-    hipLaunchKernelGGL(dd::gae_kernel, dim3((unsigned)dd::tiles_of(n)), dim3(dd::kBlock), 0, s, rewards, values,
-                       dones, advantages, returns, (int32_t)T, n, g, gl);
-    return dd::finish();
-}
-
-int dd_selftest_sqrt(uint64_t seed, int64_t n, unsigned long long* mismatches, void* stream) {
-    if (n < 0 || n > ((int64_t)1 << 40) || !mismatches) return hipErrorInvalidValue;
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    const int64_t per = (int64_t)dd::kBlock * 4096;  // lanes per launch; 4 draws per lane
-    for (int64_t first = 0; first < n; first += per * 4) {
-        const int64_t len = n - first < per * 4 ? n - first : per * 4;
-        const unsigned blocks = (unsigned)dd::tiles_of((len + 3) / 4);
-        hipLaunchKernelGGL(dd::sqrt_selftest_kernel, dim3(blocks), dim3(dd::kBlock), 0, s, seed,
-                           (uint64_t)first, len, mismatches);
-    }
-    return dd::finish();
-}
-
-int dd_stamp(unsigned long long* slot, void* stream) {
-    if (!slot) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(dd::stamp_kernel, dim3(1), dim3(dd::kWave), 0, static_cast<hipStream_t>(stream), slot);
-    return dd::finish();
-}
-
-int dd_wall_clock_khz(int* khz) {
-    if (!khz) return hipErrorInvalidValue;
-    int dev = 0;
-    hipError_t e = hipGetDevice(&dev);
-    if (e == hipSuccess) e = hipDeviceGetAttribute(khz, hipDeviceAttributeWallClockRate, dev);
-    return (int)e;
-}
-
-int64_t dd_compact_workspace(int64_t n) { return n <= 0 ? 1 : dd::tiles_of(n); }
-
-int dd_compact(const uint8_t* flags, int32_t want, int32_t* idx_out, int32_t* count, int32_t* workspace,
-               int64_t n, void* stream) {
-    if (n < 0 || n > INT32_MAX || !count || (n > 0 && (!flags || !idx_out || !workspace)))
-        return hipErrorInvalidValue;
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    if (n == 0) return (int)hipMemsetAsync(count, 0, sizeof(int32_t), s);
-    const int64_t m = dd::tiles_of(n);
-    hipLaunchKernelGGL(dd::compact_count_kernel, dim3((unsigned)m), dim3(dd::kBlock), 0, s, flags, want,
-                       workspace, n);
-    hipLaunchKernelGGL(dd::compact_scan_kernel, dim3(1), dim3(1024), 0, s, workspace, m, count);
-    hipLaunchKernelGGL(dd::compact_scatter_kernel, dim3((unsigned)m), dim3(dd::kBlock), 0, s, flags, want,
-                       (const int32_t*)workspace, idx_out, n);
-    return dd::finish();
-}
-
-int64_t dd_step_bytes_per_env(int32_t precision, int32_t action_format, int32_t with_obs) {
-    const int64_t f = precision == DD_F64 ? 8 : 4;
-    const int64_t act = action_format == DD_ACT_F32X3 ? 12 : action_format == DD_ACT_U8X3 ? 3 : 1;
-    // reads: x y vx vy angle omega fuel px py total (10 f) + status 1 + steps 4 + action
-    const int64_t rd = 10 * f + 1 + 4 + act;
-    // writes: x y vx vy angle omega fuel total reward (9 f) + steps 4 + done 1
-    // (status is rewritten only on the frame an episode ends)
-    const int64_t wr = 9 * f + 4 + 1;
-    return rd + wr + (with_obs ? DD_OBS_DIM * 4 : 0);
-}
-
-const char* dd_error_string(int code) { return hipGetErrorString((hipError_t)code); }
-
-int dd_abi_version(void) { return DD_ABI_VERSION; }
 
 }  // extern "C"
 #endif  // DD_ISA_PROBE

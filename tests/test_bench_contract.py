@@ -142,6 +142,25 @@ def test_pmc_traffic_only_for_the_measured_build(tmp_path):
     assert b.pmc_traffic_row(262144, "f32", True, str(p))[0] == 123
 
 
+def test_kernel_hashes_are_of_real_functions(tmp_path):
+    # a kernel hash of no function at all would equal itself across every edit and keep every PMC row "valid"
+    import hashlib
+    import importlib.util
+    import pytest
+    from delivery_drone_amd import abi
+    mine = dict(kv.split("=", 1) for kv in abi.lib().dd_build_info().decode().split(";"))
+    empty = hashlib.sha256().hexdigest()[:16]
+    assert mine["step_kernel_isa"] != empty and mine["rollout_kernel_isa"] != empty
+    spec = importlib.util.spec_from_file_location("build_info", os.path.join(REPO, "tools", "build_info.py"))
+    build_info = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(build_info)
+    s = tmp_path / "unit.s"
+    s.write_text("_ZN2dd11step_kernelIfEEvv:\n\ts_endpgm\n.Lfunc_end0:\n")
+    assert build_info.kernel_digest(str(s), b"_ZN2dd11step_kernel") != empty
+    with pytest.raises(ValueError, match="no function"):
+        build_info.kernel_digest(str(s), b"_ZN2dd14rollout_kernel")
+
+
 def _gather_rank(rank, world, port, outdir):
     import torch
     import torch.distributed as dist

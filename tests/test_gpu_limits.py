@@ -2,7 +2,7 @@
 
 The kernels address a lane array as SGPR base + 32-bit byte offset, so the
 host splits every launch into chunks of 2^28 lanes (kChunk in
-csrc/drone_step.hip: lane x 8 B stays below 2^31 for f64 storage) and offsets
+csrc/lane_io.h: lane x 8 B stays below 2^31 for f64 storage) and offsets
 the SoA, action, output and observation pointers per chunk.  Nothing smaller
 than 2^28 + 1 lanes runs a second chunk, so these tests build such a batch
 (~32-70 GB of device memory; MI355X has 288 GB) and check, against the

@@ -7,7 +7,7 @@ included); `--freq` weights each phase by how often a wave runs it
 (tools/lab/branch_freq.py's per-wave rates) for an estimate of the dynamic
 counts per wave.
 
-    hipcc ... -gline-tables-only --offload-device-only -S -o /tmp/ds.s csrc/drone_step.hip
+    hipcc ... -gline-tables-only --offload-device-only -S -o /tmp/ds.s csrc/step.hip
     python3 tools/isa_phases.py /tmp/ds.s '_ZN2dd11step_kernelIfLi0ELb1ELi0EEEvNS_8StepArgsENS_3SoaIT_EE'
 
 Phases (by innermost source function; frame() split by its own sections):

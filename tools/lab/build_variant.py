@@ -9,7 +9,7 @@ product sources stay free of lab switches.
     python tools/lab/build_variant.py NAME FILE OLD NEW [OLD NEW ...] [-- FILE2 OLD NEW ...]
 
 Edits to several sources are groups separated by "--".  DD_VARIANT_UNITS
-(comma list, e.g. drone_step) limits the rebuilt translation units; the
+(comma list, e.g. step) limits the rebuilt translation units; the
 others are linked from the product build (a lab timing the step kernel need
 not wait for policy_rollout.hip).
 """
@@ -20,7 +20,8 @@ import sys
 
 REPO = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 PKG = os.path.join(REPO, "reinforcement-learning-101_amd")
-UNITS = ("drone_step", "policy_mlp", "policy_rollout", "render", "device_memory")  # the Makefile's SRCS
+# the translation units: every csrc/*.hip, as the Makefile's SRCS
+UNITS = tuple(sorted(f[:-4] for f in os.listdir(os.path.join(PKG, "csrc")) if f.endswith(".hip")))
 FLAGS = {"policy_mlp": ["-mllvm", "-disable-machine-licm"], "policy_rollout": ["-mllvm", "-disable-machine-licm"]}
 
 

@@ -3,7 +3,7 @@
 gfx950: `q0 = x * inv` written over x's register, then `fma(-q0, d, x)`
 reading that register as x, i.e. `v_fma_f64 D, (-)A, B, A`.  The frame code
 never forms fma(a, b, a), so any hit is the miscompile.
-    python tools/scan_isa.py /tmp/isa/drone_step.s"""
+    python tools/scan_isa.py /tmp/isa/rollout.s"""
 import re
 import sys
 
