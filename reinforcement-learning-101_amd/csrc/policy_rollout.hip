@@ -135,10 +135,7 @@ __device__ __forceinline__ void next_input(const Consts& k, const Lane& s, int h
     double v[13];
     observe_values<kGuard>(k, s, v);
     float o[16];
-#pragma unroll
-    for (int j = 0; j < 13; ++j) o[j] = (float)v[j];
-    o[13] = (s.status & DD_ST_LANDED) ? 1.0f : 0.0f;
-    o[14] = (s.status & DD_ST_CRASHED) ? 1.0f : 0.0f;
+    write_obs_row(v, s.status, o);
     o[15] = 0.0f;
 #pragma unroll
     for (int q = 0; q < 8; ++q) x[q] = h ? o[in_col<kSplit>(q, 1)] : o[in_col<kSplit>(q, 0)];
@@ -337,21 +334,19 @@ hipError_t launch(const float* packed, const P& p, const Soa<T>& a, hipStream_t 
     return hipGetLastError();
 }
 
-template <typename T, bool kSplit, typename P>
-hipError_t launch_ref(bool ref, const float* packed, const P& p, const Soa<T>& a, hipStream_t s) {
-    return ref ? launch<T, kSplit, true>(packed, p, a, s) : launch<T, kSplit, false>(packed, p, a, s);
-}
-
+// The kernel for a state's storage width, the actor's arithmetic and the physics (launch.h).  The width
+// through with_bool, not with_storage: double first keeps the unit's kernels in the order they had (the
+// order of instantiation is the order of the device code, which policy_rollout_isa hashes).
 template <typename P>
-hipError_t launch_any(const DDState& st, int32_t compute, bool ref, const float* packed, const P& p, hipStream_t s) {
-    if (st.precision == DD_F64) {
-        const Soa<double> a = soa_of<double>(st, 0);
-        return compute == DD_MLP_F16X3 ? launch_ref<double, true>(ref, packed, p, a, s)
-                                       : launch_ref<double, false>(ref, packed, p, a, s);
-    }
-    const Soa<float> a = soa_of<float>(st, 0);
-    return compute == DD_MLP_F16X3 ? launch_ref<float, true>(ref, packed, p, a, s)
-                                   : launch_ref<float, false>(ref, packed, p, a, s);
+hipError_t launch_for(const DDState& st, int32_t compute, bool ref, const float* packed, const P& p, hipStream_t s) {
+    return with_bool(st.precision == DD_F64, [&](auto f64) {
+        using T = std::conditional_t<decltype(f64)::value, double, float>;
+        return with_bool(compute == DD_MLP_F16X3, [&](auto split) {
+            return with_bool(ref, [&](auto r) {
+                return launch<T, decltype(split)::value, decltype(r)::value>(packed, p, soa_of<T>(st, 0), s);
+            });
+        });
+    });
 }
 
 }  // namespace prl
@@ -381,10 +376,8 @@ extern "C" int dd_policy_rollout_sampled(const DDConfig* cfg, const DDState* st,
         with_stats = set == 4;
     }
     if (compute != DD_MLP_F32 && compute != DD_MLP_F16X3) return hipErrorInvalidValue;
-    if ((io->engine_reward == nullptr) != (io->engine_done == nullptr)) return hipErrorInvalidValue;
-    if (io->shaped_mode != DD_SHAPED_PPO && io->shaped_mode != DD_SHAPED_REINFORCE) return hipErrorInvalidValue;
-    const int shape = dd::shape_of(io->shaped_mode, io->shaped_hist, nullptr);
-    if (io->engine_reward && shape == dd::kShapeNone) return hipErrorInvalidValue;
+    const int shape = dd::loop_shape(io->shaped_mode, io->shaped_hist, io->engine_reward, io->engine_done);
+    if (shape < 0) return hipErrorInvalidValue;
     if (n == 0) return hipSuccess;
     // the per-frame buffers are optional only next to the statistics
     if (!packed || !io->obs0 || (io->frames > 0 && !with_stats && (!io->reward || !io->done)))
@@ -415,7 +408,7 @@ extern "C" int dd_policy_rollout_sampled(const DDConfig* cfg, const DDState* st,
     const hipStream_t s = (hipStream_t)stream;
     // the plain Bernoulli draw with no probs_used and no statistics is the collection kernel
     const bool eval = with_stats || (sampling && (sampling->mode != DD_SAMPLE_BERNOULLI || sampling->probs_used));
-    if (!eval) return (int)dd::prl::launch_any(*st, compute, ref, packed, p, s);
+    if (!eval) return (int)dd::prl::launch_for(*st, compute, ref, packed, p, s);
     dd::prl::EvalArgs q{};
     static_cast<dd::prl::Args&>(q) = p;
     q.mode = sampling ? sampling->mode : DD_SAMPLE_BERNOULLI;
@@ -427,5 +420,5 @@ extern "C" int dd_policy_rollout_sampled(const DDConfig* cfg, const DDState* st,
         q.ep_status = stats->ep_status;
         q.ep_fuel = stats->ep_fuel;
     }
-    return (int)dd::prl::launch_any(*st, compute, ref, packed, q, s);
+    return (int)dd::prl::launch_for(*st, compute, ref, packed, q, s);
 }

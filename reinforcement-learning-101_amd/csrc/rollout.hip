@@ -655,25 +655,6 @@ void launch_rollout(const RolloutArgs& p, int kind, const Soa<T>& a, hipStream_t
         hipLaunchKernelGGL((rollout_kernel<T, AFMT, kRef, false, kShape>), dim3(blocks), dim3(kBlock), 0, s, p, a);
 }
 
-template <typename T, bool kRef, int kShape>
-void launch_rollout_fmt(const RolloutArgs& p, int kind, int afmt, const Soa<T>& a, hipStream_t s) {
-    switch (afmt) {
-        case DD_ACT_BITMASK: launch_rollout<T, DD_ACT_BITMASK, kRef, kShape>(p, kind, a, s); break;
-        case DD_ACT_F32X3: launch_rollout<T, DD_ACT_F32X3, kRef, kShape>(p, kind, a, s); break;
-        case DD_ACT_U8X3: launch_rollout<T, DD_ACT_U8X3, kRef, kShape>(p, kind, a, s); break;
-        default: launch_rollout<T, DD_ACT_PHILOX, kRef, kShape>(p, kind, a, s); break;
-    }
-}
-
-template <typename T, bool kRef>
-void launch_rollout_shape(const RolloutArgs& p, int kind, int shape, int afmt, const Soa<T>& a, hipStream_t s) {
-    switch (shape) {
-        case kShapeNone: launch_rollout_fmt<T, kRef, kShapeNone>(p, kind, afmt, a, s); break;
-        case kShapePpo: launch_rollout_fmt<T, kRef, kShapePpo>(p, kind, afmt, a, s); break;
-        default: launch_rollout_fmt<T, kRef, kShapeReinforce>(p, kind, afmt, a, s); break;
-    }
-}
-
 template <typename T>
 void rollout_chunks(RolloutArgs p, const DDState& st, const DDRolloutIO& io, int64_t n, hipStream_t s) {
     const bool ref = uses_reference_physics(p.k.c);
@@ -713,8 +694,13 @@ void rollout_chunks(RolloutArgs p, const DDState& st, const DDRolloutIO& io, int
             p.max_steps = io.max_steps;
             const Soa<T> a = soa_of<T>(st, first);
             const int kind = rollout_kernel_for(ref, shape, io.action_format, p.actions, p.obs, n, len, io.kernel);
-            if (ref) launch_rollout_shape<T, true>(p, kind, shape, io.action_format, a, s);
-            else launch_rollout_shape<T, false>(p, kind, shape, io.action_format, a, s);
+            with_bool(ref, [&](auto r) {
+                with_value<kShapeNone, kShapePpo, kShapeReinforce>(shape, [&](auto sh) {
+                    with_value<DD_ACT_BITMASK, DD_ACT_F32X3, DD_ACT_U8X3, DD_ACT_PHILOX>(io.action_format, [&](auto fmt) {
+                        launch_rollout<T, decltype(fmt)::value, decltype(r)::value, decltype(sh)::value>(p, kind, a, s);
+                    });
+                });
+            });
         }
     });
 }
@@ -730,9 +716,7 @@ int dd_rollout(const DDConfig* cfg, const DDState* st, const DDRolloutIO* io, in
     if (n == 0 || io->frames == 0) return 0;
     if (!dd::state_ok(st) || !io->reward || !io->done) return hipErrorInvalidValue;
     if (io->action_format != DD_ACT_PHILOX && !io->actions) return hipErrorInvalidValue;
-    if ((io->engine_reward != nullptr) != (io->engine_done != nullptr)) return hipErrorInvalidValue;
-    if (io->shaped_mode != DD_SHAPED_PPO && io->shaped_mode != DD_SHAPED_REINFORCE) return hipErrorInvalidValue;
-    if (io->engine_reward && dd::shape_of(io->shaped_mode, io->shaped_hist, nullptr) == dd::kShapeNone)
+    if (dd::loop_shape(io->shaped_mode, io->shaped_hist, io->engine_reward, io->engine_done) < 0)
         return hipErrorInvalidValue;
     if (io->kernel < DD_ROLLOUT_AUTO || io->kernel > DD_ROLLOUT_SPLIT_NO_WAIT) return hipErrorInvalidValue;
     hipStream_t s = static_cast<hipStream_t>(stream);

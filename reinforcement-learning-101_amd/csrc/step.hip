@@ -235,24 +235,6 @@ void launch_step(const StepArgs& p, const Soa<T>& a, const Soa<T>* o, hipStream_
         hipLaunchKernelGGL((step_kernel<T, AFMT, kRef, kShape>), dim3(blocks), dim3(kStepBlock), 0, s, p, a);
 }
 
-template <typename T, bool kRef, int kShape>
-void launch_step_fmt(const StepArgs& p, int afmt, const Soa<T>& a, const Soa<T>* o, hipStream_t s) {
-    switch (afmt) {
-        case DD_ACT_BITMASK: launch_step<T, DD_ACT_BITMASK, kRef, kShape>(p, a, o, s); break;
-        case DD_ACT_F32X3: launch_step<T, DD_ACT_F32X3, kRef, kShape>(p, a, o, s); break;
-        default: launch_step<T, DD_ACT_U8X3, kRef, kShape>(p, a, o, s); break;
-    }
-}
-
-template <typename T, bool kRef>
-void launch_step_shape(const StepArgs& p, int shape, int afmt, const Soa<T>& a, const Soa<T>* o, hipStream_t s) {
-    switch (shape) {
-        case kShapeNone: launch_step_fmt<T, kRef, kShapeNone>(p, afmt, a, o, s); break;
-        case kShapePpo: launch_step_fmt<T, kRef, kShapePpo>(p, afmt, a, o, s); break;
-        default: launch_step_fmt<T, kRef, kShapeReinforce>(p, afmt, a, o, s); break;
-    }
-}
-
 template <typename T>
 void step_chunks(StepArgs p, const DDState& st, const DDStepIO& io, int64_t n, hipStream_t s) {
     const bool ref = uses_reference_physics(p.k.c);
@@ -273,8 +255,14 @@ void step_chunks(StepArgs p, const DDState& st, const DDStepIO& io, int64_t n, h
         const Soa<T> a = soa_of<T>(st, first);
         Soa<T> o;
         if (io.state_out) o = soa_of<T>(*io.state_out, first);
-        if (ref) launch_step_shape<T, true>(p, shape, io.action_format, a, io.state_out ? &o : nullptr, s);
-        else launch_step_shape<T, false>(p, shape, io.action_format, a, io.state_out ? &o : nullptr, s);
+        with_bool(ref, [&](auto r) {
+            with_value<kShapeNone, kShapePpo, kShapeReinforce>(shape, [&](auto sh) {
+                with_value<DD_ACT_BITMASK, DD_ACT_F32X3, DD_ACT_U8X3>(io.action_format, [&](auto fmt) {
+                    launch_step<T, decltype(fmt)::value, decltype(r)::value, decltype(sh)::value>(
+                        p, a, io.state_out ? &o : nullptr, s);
+                });
+            });
+        });
     });
 }
 

@@ -112,6 +112,34 @@ def test_policy_rollout_notebook_reward_and_timeout(mode, compute, gpu_device):
     assert bool((rew < -400).any())  # max_steps timeouts (-500) happened inside the launch
 
 
+@pytest.mark.parametrize("precision", ["f32", "f64"])
+@pytest.mark.parametrize("mode", ["notebook", "reinforce"])
+def test_policy_rollout_notebook_reward_sticky_done(mode, precision, gpu_device):
+    # auto_reset off, in the collection kernel: every lane alive at frame 12 times out (max_steps) and
+    # then sits sticky-done for eight frames.  70 drones: two full 32-drone wave tiles and a ragged one,
+    # n % 4 != 0 (the unaligned row path)
+    n, frames = 70, 20
+    net = actor(gpu_device, 5, "f16x3")
+    fused, ref = twins(n, gpu_device, precision, reward_mode=mode, max_steps=12, randomize_drone=True,
+                       auto_reset=False, seed=13)
+    e_rew = torch.empty(frames, n, dtype=fused.float_dtype, device=gpu_device)
+    e_done = torch.empty(frames, n, dtype=torch.bool, device=gpu_device)
+    obs, acts, lp, rew, done = fused.policy_rollout(net, frames, seed=9, engine_reward_out=e_rew,
+                                                    engine_done_out=e_done)
+    r_obs, r_acts, r_lp, r_rew, r_done, r_erew, r_edone = loop(ref, net, frames, 9, 0)
+    for got, want in zip((acts, lp, rew, done, e_rew, e_done), (r_acts, r_lp, r_rew, r_done, r_erew, r_edone)):
+        assert torch.equal(got, want)
+    got, want = fused.state_dict(), ref.state_dict()
+    assert got.keys() == want.keys() and ("shaped_hist" in got) == (mode == "notebook")
+    for key in want:
+        g, w = got[key], want[key]
+        if key == "shaped_hist":  # bit patterns: NaN ("prev_state None") never equals itself
+            g, w = g.view(torch.int64), w.view(torch.int64)
+        assert torch.equal(g, w), key
+    assert bool(done[11:].all()) and bool((rew[11] < -400).any())  # the timeout, then sticky done
+    assert bool((rew[12:] == 0).all()) and bool((e_rew[12:] == 0).all())
+
+
 def test_policy_rollout_many_blocks_and_options(gpu_device):
     # 70,001 drones: more 8-wave blocks than CUs, a ragged last tile, rows not 16-byte aligned
     n, frames = 70_001, 6
