@@ -548,6 +548,103 @@ int dd_wall_clock_khz(int *khz);
 int dd_device_alloc(void **ptr, uint64_t bytes, int32_t flags);
 int dd_device_free(void *ptr);
 
+/* ---- Training batches from rollout buffers ------------------------------
+ * The stretch between a finished rollout and the tensors the notebooks' loss
+ * functions take: Actor_Critic_PPO.ipynb's training cell ("PHASE 2": per
+ * episode stack the states, run the critic, compute_gae, returns = advantages
+ * + values; then torch.cat over the episodes and normalise the advantages),
+ * and Policy_Gradients.ipynb's (per episode compute_returns; then the
+ * baseline and the same normalisation).  The input is one rollout as the
+ * policy rollout returns it: done uint8 [T][N], reward [T][N], and optionally
+ * obs float [T][N][15], actions uint8 bitmasks [T][N], log_prob float [T][N].
+ * Only each lane's FIRST episode counts, and the layout is decided by `done`
+ * alone (the same on a sticky-done and an auto-reset env).
+ *
+ * DDBatchLayout (caller-owned, device): length int32 [N], (first t with
+ * done[t][i] != 0) + 1 or T if there is none; ended uint8 [N], which of the
+ * two; offset int64 [N + 1], the exclusive prefix sum of length, offset[N] =
+ * M the batch size.  Row offset[i] + t of every flat buffer is lane i's frame
+ * t: episode-major, the order of the notebook's torch.cat.  All index
+ * arithmetic is 64-bit.
+ *
+ * The plan writes a DDBatchLayout (deterministic scan; the host reads M =
+ * offset[N] to size the flat buffers); the other stages read it.  workspace:
+ * the workspace function's count of bytes, 8-byte aligned, shared by the plan
+ * and the normalisation (calls on one stream may reuse it). */
+typedef struct DDBatchLayout {
+    int32_t *length;
+    int64_t *offset;
+    uint8_t *ended;
+} DDBatchLayout;
+
+int64_t dd_batch_workspace(int64_t n);
+int dd_batch_plan(const uint8_t *done, int64_t T, int64_t n, const DDBatchLayout *layout,
+                  void *workspace, void *stream);
+
+/* Gather (the notebook's torch.stack per episode + torch.cat): states [M][15]
+ * from obs, actions_out float [M][3] = 1.0 / 0.0 in (main, left, right) order
+ * (the Bernoulli.sample() layout compute_ppo_losses consumes) from the
+ * bitmasks, old_log_probs [M] from log_prob.  Each input is optional together
+ * with its output (one without the other: hipErrorInvalidValue).  No row >=
+ * M is written.  tile_frames: the frames of one LDS tile (64 lanes x
+ * tile_frames frames per block), 8 or 16, 0 = the default (8). */
+typedef struct DDBatchGatherIO {
+    const float *obs;
+    const uint8_t *actions;
+    const float *log_prob;
+    float *states;
+    float *actions_out;
+    float *old_log_probs;
+    int32_t tile_frames;
+    int32_t _pad;
+} DDBatchGatherIO;
+
+int dd_batch_gather(const DDBatchLayout *layout, const DDBatchGatherIO *io, int64_t T, int64_t n,
+                    void *stream);
+
+/* Advantages over the flat layout, one episode per lane.  Both modes write
+ * episode_return double [N] (nullable): the lane's rewards summed in frame
+ * order in double, the notebooks' sum(rewards).
+ * DD_BATCH_GAE (Actor_Critic_PPO.ipynb:733-787 as its training cell calls it):
+ *   values float [M] (the critic on the gathered states), bootstrap float [N]
+ *   (nullable = 0): the value of the state after frame T-1, used only by
+ *   lanes with ended == 0.  dones is all false but the last frame of an ended
+ *   episode; rewards are rounded to float32 first; the recursion is the
+ *   rectangular GAE's, bit for bit.  advantages float [M], returns (nullable)
+ *   = advantages + values.
+ * DD_BATCH_RETURNS (compute_returns, Policy_Gradients.ipynb): G = r + gamma *
+ *   G backwards in double on the reward as stored, rounded to float32 once
+ *   (torch.tensor(batch_returns, dtype=float32)) into returns float [M].
+ * precision: the reward's storage, DD_F32 or DD_F64. */
+#define DD_BATCH_GAE 0
+#define DD_BATCH_RETURNS 1
+typedef struct DDBatchAdvIO {
+    const void *reward;
+    int32_t precision;
+    int32_t mode;
+    const float *values;
+    const float *bootstrap;
+    float *advantages;
+    float *returns;
+    double *episode_return;
+    double gamma;
+    double lambda;
+} DDBatchAdvIO;
+
+int dd_batch_advantages(const DDBatchLayout *layout, const DDBatchAdvIO *io, int64_t T, int64_t n,
+                        void *stream);
+
+/* Batch statistics and normalisation of x float [m] (the advantages, or
+ * REINFORCE's returns): *mean and *std (device doubles; std unbiased, as
+ * torch.std's default) accumulated in double by a reduction tree of fixed
+ * shape (no atomics: the same bits on every run), and out (nullable; may be
+ * x) = (x - mean) / (std + 1e-8) evaluated in double and rounded to float32
+ * once: the notebooks' `(a - a.mean()) / (a.std() + 1e-8)`, and for REINFORCE
+ * equally its baseline subtraction followed by that line (mean = the
+ * baseline).  m < 2: std and out are NaN, as torch's. */
+int dd_batch_normalize(const float *x, float *out, int64_t m, double *mean, double *std,
+                       void *workspace, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -8,6 +8,7 @@
 
 #include "dronestep.h"
 #include "frame.h"
+#include "gae_core.h"
 #include "lane_io.h"
 #include "launch.h"
 #include "philox.h"
@@ -121,9 +122,9 @@ __global__ __launch_bounds__(kBlock) void info_kernel(Soa<T> a, T* distance, T* 
 // ---------------------------------------------------------------------------
 // dd_gae: one lane per env walks its column of the [T][N] rollout backwards.
 // The loads of a frame do not depend on the running gae, so the compiler
-// keeps several frames' loads in flight (unroll 4).  Float32 throughout, in
-// compute_gae's order: torch evaluates `gamma * v` with gamma rounded to
-// float32 and `gamma * lambda_` in Python doubles before that rounding.
+// keeps several frames' loads in flight (unroll 4).  The recursion itself is
+// gae_core.h's gae_frame (float32, compute_gae's operation order), which the
+// ragged scan of train_batch.hip shares.
 // ---------------------------------------------------------------------------
 __global__ __launch_bounds__(kBlock) void gae_kernel(const float* __restrict__ rewards,
                                                      const float* __restrict__ values,
@@ -150,9 +151,7 @@ __global__ __launch_bounds__(kBlock) void gae_kernel(const float* __restrict__ r
 #pragma unroll
         for (int j = 0; j < kG; ++j) {
             const int64_t o = (int64_t)(t - j) * n + i;
-            const float mask = 1.0f - d[j];
-            const float delta = (r[j] + (g * v_next) * mask) - v[j];
-            gae = delta + (gl * mask) * gae;
+            gae_frame(r[j], v[j], v_next, 1.0f - d[j], g, gl, gae);
             __builtin_nontemporal_store(gae, adv + o);
             if (ret) __builtin_nontemporal_store(gae + v[j], ret + o);
             v_next = v[j];
@@ -161,9 +160,7 @@ __global__ __launch_bounds__(kBlock) void gae_kernel(const float* __restrict__ r
     for (; t >= 0; --t) {
         const int64_t o = (int64_t)t * n + i;
         const float v = values[o];
-        const float mask = 1.0f - (float)dones[o];
-        const float delta = (rewards[o] + (g * v_next) * mask) - v;
-        gae = delta + (gl * mask) * gae;
+        gae_frame(rewards[o], v, v_next, 1.0f - (float)dones[o], g, gl, gae);
         __builtin_nontemporal_store(gae, adv + o);
         if (ret) __builtin_nontemporal_store(gae + v, ret + o);
         v_next = v;

@@ -8,7 +8,9 @@ surface (:class:`VecDroneEnv`) and the reference's per-game APIs
 policy / value networks (:class:`MlpNet`, f32 MFMA) and GAE (:func:`gae`)
 for on-device collection, and the notebooks' ``evaluate_policy`` (temperature
 or greedy action selection, one episode per lane:
-:meth:`VecDroneEnv.evaluate_policy`).
+:meth:`VecDroneEnv.evaluate_policy`); and the notebooks' training batches
+built from rollout buffers on device (:func:`ppo_batch`,
+:func:`reinforce_batch`, :func:`collect_ppo`).
 """
 from .config import EnvConfig
 from .vec_env import OBS_KEYS, StepInfo, VecDroneEnv
@@ -16,10 +18,12 @@ from .compat import DroneGame, DroneGameClient, DroneState, action_bits
 from .sharding import dist_env, gather_obs, shard_bounds
 from .gae import gae
 from .policy import MlpNet
+from .train_batch import collect_ppo, ppo_batch, reinforce_batch
 
 __all__ = [
     "EnvConfig", "VecDroneEnv", "StepInfo", "OBS_KEYS",
     "DroneGame", "DroneGameClient", "DroneState", "action_bits",
     "shard_bounds", "dist_env", "gather_obs", "gae", "MlpNet",
+    "ppo_batch", "reinforce_batch", "collect_ppo",
 ]
 __version__ = "0.1.0"

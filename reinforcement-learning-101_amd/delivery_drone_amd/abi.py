@@ -20,7 +20,8 @@ __all__ = [
     "DD_ROLLOUT_FLUSHED", "DD_ROLLOUT_HELD", "DD_ROLLOUT_SPLIT", "DD_ERR_HANDOVER",
     "DD_SAMPLE_BERNOULLI", "DD_SAMPLE_TEMPERED", "DD_SAMPLE_GREEDY",
     "DDConfig", "DDState", "DDStepIO", "DDRolloutIO", "DDMlpParams", "DDMlpIO", "DDPolicyRolloutIO", "DDSampling",
-    "DDEpisodeStats", "sampling_mode", "lib", "load", "library_path", "check",
+    "DDEpisodeStats", "DD_BATCH_GAE", "DD_BATCH_RETURNS", "DDBatchLayout", "DDBatchGatherIO", "DDBatchAdvIO",
+    "sampling_mode", "lib", "load", "library_path", "check",
     "NativeLibraryError",
 ]
 
@@ -37,6 +38,7 @@ DD_ROLLOUT_FLUSHED, DD_ROLLOUT_HELD, DD_ROLLOUT_SPLIT = 16, 17, 18
 DD_ERR_HANDOVER = 1
 DD_MEM_DEFAULT, DD_MEM_CONTIGUOUS = 0, 1
 DD_SAMPLE_BERNOULLI, DD_SAMPLE_TEMPERED, DD_SAMPLE_GREEDY = 0, 1, 2
+DD_BATCH_GAE, DD_BATCH_RETURNS = 0, 1
 
 _D = ctypes.c_double
 _I = ctypes.c_int32
@@ -137,6 +139,22 @@ class DDEpisodeStats(ctypes.Structure):
                 ("ep_fuel", ctypes.c_void_p)]
 
 
+class DDBatchLayout(ctypes.Structure):
+    _fields_ = [("length", ctypes.c_void_p), ("offset", ctypes.c_void_p), ("ended", ctypes.c_void_p)]
+
+
+class DDBatchGatherIO(ctypes.Structure):
+    _fields_ = [("obs", ctypes.c_void_p), ("actions", ctypes.c_void_p), ("log_prob", ctypes.c_void_p),
+                ("states", ctypes.c_void_p), ("actions_out", ctypes.c_void_p), ("old_log_probs", ctypes.c_void_p),
+                ("tile_frames", _I), ("_pad", _I)]
+
+
+class DDBatchAdvIO(ctypes.Structure):
+    _fields_ = [("reward", ctypes.c_void_p), ("precision", _I), ("mode", _I), ("values", ctypes.c_void_p),
+                ("bootstrap", ctypes.c_void_p), ("advantages", ctypes.c_void_p), ("returns", ctypes.c_void_p),
+                ("episode_return", ctypes.c_void_p), ("gamma", _D), ("lambda_", _D)]
+
+
 def sampling_mode(temperature) -> int:
     """The ``DD_SAMPLE_*`` mode of a notebook ``temperature``: 1 is the plain
     Bernoulli draw, 0 greedy (``probs > 0.5``), any other positive finite value
@@ -198,13 +216,23 @@ EXPORTS = {
     "dd_wall_clock_khz": (ctypes.c_int, [ctypes.POINTER(ctypes.c_int)]),
     "dd_device_alloc": (ctypes.c_int, [ctypes.POINTER(ctypes.c_void_p), ctypes.c_uint64, _I]),
     "dd_device_free": (ctypes.c_int, [ctypes.c_void_p]),
+    "dd_batch_workspace": (ctypes.c_int64, [ctypes.c_int64]),
+    "dd_batch_plan": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.POINTER(DDBatchLayout),
+                                     ctypes.c_void_p, ctypes.c_void_p]),
+    "dd_batch_gather": (ctypes.c_int, [ctypes.POINTER(DDBatchLayout), ctypes.POINTER(DDBatchGatherIO),
+                                       ctypes.c_int64, ctypes.c_int64, ctypes.c_void_p]),
+    "dd_batch_advantages": (ctypes.c_int, [ctypes.POINTER(DDBatchLayout), ctypes.POINTER(DDBatchAdvIO),
+                                           ctypes.c_int64, ctypes.c_int64, ctypes.c_void_p]),
+    "dd_batch_normalize": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p,
+                                          ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
 }
 
 #: symbols a timing-only lab build (tools/build_variants.sh) or an older
 #: committed source built for an A/B run may lack
 _LAB_OPTIONAL = ("dd_build_info", "dd_selftest_sqrt", "dd_rollout_kernel", "dd_device_errors", "dd_stamp",
                  "dd_wall_clock_khz", "dd_device_alloc", "dd_device_free", "dd_mlp_forward_sampled",
-                 "dd_policy_rollout_sampled")
+                 "dd_policy_rollout_sampled", "dd_batch_workspace", "dd_batch_plan", "dd_batch_gather",
+                 "dd_batch_advantages", "dd_batch_normalize")
 
 
 class NativeLibraryError(RuntimeError):

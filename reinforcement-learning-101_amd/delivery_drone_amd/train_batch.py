@@ -1,0 +1,221 @@
+"""PPO and REINFORCE training batches from rollout buffers, on device.
+
+The stretch between a finished rollout and the tensors the notebooks' loss
+functions take.  In the reference it is a host loop over episodes
+(Actor_Critic_PPO.ipynb's training cell, "PHASE 2": stack the states, run the
+critic, ``compute_gae``, ``returns = advantages + values``, then ``torch.cat``
+and the batch normalisation; Policy_Gradients.ipynb's: ``compute_returns``,
+the baseline and the same normalisation).  Here the input is one rollout as
+:meth:`VecDroneEnv.policy_rollout` returns it, ``[frames, N]`` buffers in which
+every lane's episode has its own length, and four stages of
+``csrc/train_batch.hip`` build the ragged batch:
+
+* plan: each lane's first-episode ``length`` (first done + 1, or ``frames``),
+  ``ended`` and the row ``offset`` (exclusive scan; ``offset[N] = M``).  Row
+  ``offset[i] + t`` of every flat tensor is lane ``i``'s frame ``t``:
+  episode-major, the order of the notebook's ``torch.cat``.  The wrapper reads
+  ``M`` once (the one synchronisation per batch) and allocates exact sizes.
+* gather: ``states [M, 15]``, ``actions [M, 3]`` float (main, left, right),
+  ``old_log_probs [M]``.
+* advantages: ``compute_gae`` per episode on the critic's values of the ``M``
+  gathered rows (bit for bit :func:`~delivery_drone_amd.gae` on the valid
+  rows), or ``compute_returns`` in double; and ``sum(rewards)`` per episode.
+* normalise: ``(a - mean) / (std + 1e-8)``, mean and unbiased std accumulated
+  in double in a fixed order (the same bits on every run).  With fewer than
+  two rows (``M < 2``) std and the normalised values are NaN, as torch's.
+"""
+from __future__ import annotations
+
+import ctypes
+from typing import NamedTuple, Optional
+
+import torch
+
+from . import abi
+
+__all__ = ["PpoBatch", "ReinforceBatch", "ppo_batch", "reinforce_batch", "collect_ppo"]
+
+
+class PpoBatch(NamedTuple):
+    states: Optional[torch.Tensor]         # [M, 15]
+    actions: Optional[torch.Tensor]        # [M, 3] float32, 1.0 / 0.0 (main, left, right)
+    old_log_probs: Optional[torch.Tensor]  # [M]
+    advantages: torch.Tensor               # [M], normalised unless normalize=False
+    returns: torch.Tensor                  # [M] = raw advantages + values
+    values: torch.Tensor                   # [M], the critic on states
+    lengths: torch.Tensor                  # [N] int32
+    offsets: torch.Tensor                  # [N + 1] int64, offsets[N] = M
+    ended: torch.Tensor                    # [N] bool
+    episode_return: torch.Tensor           # [N] float64, sum(rewards)
+    adv_mean: torch.Tensor                 # 0-d float64, of the raw advantages
+    adv_std: torch.Tensor                  # 0-d float64, unbiased
+
+
+class ReinforceBatch(NamedTuple):
+    states: Optional[torch.Tensor]
+    actions: Optional[torch.Tensor]
+    returns: torch.Tensor                  # [M] discounted returns, float32
+    advantages: torch.Tensor               # [M] (returns - baseline) / (std + 1e-8); returns with normalize=False
+    baseline: torch.Tensor                 # 0-d float64, mean of returns
+    std: torch.Tensor                      # 0-d float64, unbiased
+    lengths: torch.Tensor
+    offsets: torch.Tensor
+    ended: torch.Tensor
+    episode_return: torch.Tensor
+
+
+def _stream(dev):
+    return ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+
+
+def _ptr(t: Optional[torch.Tensor]):
+    return t.data_ptr() if t is not None else None
+
+
+def _rollout_buffer(t, shape, dtype, dev, what):
+    """An optional [T, N(, 15)] rollout buffer: checked, never copied."""
+    if t is None:
+        return None
+    if not isinstance(t, torch.Tensor) or tuple(t.shape) != shape:
+        raise ValueError(f"{what} must be a tensor of shape {shape}, got "
+                         f"{tuple(t.shape) if isinstance(t, torch.Tensor) else type(t).__name__}")
+    if t.device != dev:
+        raise ValueError(f"{what} is on {t.device}, done on {dev}")
+    if t.dtype != dtype and not (dtype == torch.uint8 and t.dtype == torch.bool):
+        raise ValueError(f"{what} must be {dtype}, got {t.dtype}")
+    if not t.is_contiguous():
+        raise ValueError(f"{what} must be contiguous")
+    return t.view(torch.uint8) if t.dtype == torch.bool else t
+
+
+class _Plan:
+    """The layout of one rollout's batch and what the later stages need of it."""
+
+    def __init__(self, done: torch.Tensor):
+        if not isinstance(done, torch.Tensor) or done.dim() != 2:
+            raise ValueError("done must be [T, N]")
+        if done.device.type != "cuda":
+            raise ValueError("training batches are built on the GPU; move the rollout to a CUDA/HIP device")
+        if done.dtype not in (torch.bool, torch.uint8):
+            raise ValueError(f"done must be bool or uint8, got {done.dtype}")
+        if not done.is_contiguous():
+            raise ValueError("done must be contiguous")
+        self.T, self.n = (int(s) for s in done.shape)
+        self.dev = dev = done.device
+        self.done = done.view(torch.uint8) if done.dtype == torch.bool else done
+        self.lib = abi.lib()
+        n = self.n
+        self.lengths = torch.empty(n, dtype=torch.int32, device=dev)
+        self.offsets = torch.empty(n + 1, dtype=torch.int64, device=dev)
+        self.ended = torch.empty(n, dtype=torch.uint8, device=dev)
+        self.workspace = torch.empty(int(self.lib.dd_batch_workspace(n)) // 8, dtype=torch.int64, device=dev)
+        self.layout = abi.DDBatchLayout(self.lengths.data_ptr(), self.offsets.data_ptr(), self.ended.data_ptr())
+        abi.check(self.lib.dd_batch_plan(self.done.data_ptr(), self.T, n, ctypes.byref(self.layout),
+                                         self.workspace.data_ptr(), _stream(dev)), "dd_batch_plan")
+        self.M = int(self.offsets[n].item())  # the one synchronisation: the flat tensors' size
+
+    def gather(self, obs, actions, log_prob, tile_frames: int = 0):
+        T, n, dev, M = self.T, self.n, self.dev, self.M
+        obs = _rollout_buffer(obs, (T, n, abi.DD_OBS_DIM), torch.float32, dev, "obs")
+        actions = _rollout_buffer(actions, (T, n), torch.uint8, dev, "actions")
+        log_prob = _rollout_buffer(log_prob, (T, n), torch.float32, dev, "log_prob")
+        states = torch.empty(M, abi.DD_OBS_DIM, dtype=torch.float32, device=dev) if obs is not None else None
+        acts = torch.empty(M, 3, dtype=torch.float32, device=dev) if actions is not None else None
+        lps = torch.empty(M, dtype=torch.float32, device=dev) if log_prob is not None else None
+        io = abi.DDBatchGatherIO(_ptr(obs), _ptr(actions), _ptr(log_prob), _ptr(states), _ptr(acts), _ptr(lps),
+                                 int(tile_frames), 0)
+        abi.check(self.lib.dd_batch_gather(ctypes.byref(self.layout), ctypes.byref(io), T, n, _stream(dev)),
+                  "dd_batch_gather")
+        return states, acts, lps
+
+    def advantages(self, reward, mode, gamma, lambda_=0.0, values=None, bootstrap=None):
+        T, n, dev, M = self.T, self.n, self.dev, self.M
+        if not isinstance(reward, torch.Tensor) or reward.dtype not in (torch.float32, torch.float64):
+            raise ValueError("reward must be a float32 or float64 tensor")
+        reward = _rollout_buffer(reward, (T, n), reward.dtype, dev, "reward")
+        adv = torch.empty(M, dtype=torch.float32, device=dev) if mode == abi.DD_BATCH_GAE else None
+        ret = torch.empty(M, dtype=torch.float32, device=dev)
+        ep = torch.empty(n, dtype=torch.float64, device=dev)
+        io = abi.DDBatchAdvIO(reward.data_ptr(), abi.DD_F64 if reward.dtype == torch.float64 else abi.DD_F32, mode,
+                              _ptr(values), _ptr(bootstrap), _ptr(adv), ret.data_ptr(), ep.data_ptr(),
+                              float(gamma), float(lambda_))
+        abi.check(self.lib.dd_batch_advantages(ctypes.byref(self.layout), ctypes.byref(io), T, n, _stream(dev)),
+                  "dd_batch_advantages")
+        return adv, ret, ep
+
+    def normalize(self, x: torch.Tensor, normalize: bool):
+        """(mean, std, normalised x or x itself)."""
+        stats = torch.empty(2, dtype=torch.float64, device=self.dev)
+        out = torch.empty_like(x) if normalize else None
+        abi.check(self.lib.dd_batch_normalize(x.data_ptr(), _ptr(out), self.M, stats[0:].data_ptr(),
+                                              stats[1:].data_ptr(), self.workspace.data_ptr(), _stream(self.dev)),
+                  "dd_batch_normalize")
+        return stats[0], stats[1], out if normalize else x
+
+
+def _values(critic, rows: torch.Tensor, what: str) -> torch.Tensor:
+    with torch.no_grad():
+        v = critic(rows)
+    if not isinstance(v, torch.Tensor) or v.numel() != rows.shape[0]:
+        raise ValueError(f"critic({what}) must give one value per row")
+    if v.device != rows.device:
+        raise ValueError(f"critic({what}) is on {v.device}, the rollout on {rows.device}")
+    return v.detach().reshape(-1).to(torch.float32).contiguous()
+
+
+def ppo_batch(obs: torch.Tensor, actions: Optional[torch.Tensor], log_prob: Optional[torch.Tensor],
+              reward: torch.Tensor, done: torch.Tensor, critic, bootstrap_obs: Optional[torch.Tensor] = None,
+              gamma: float = 0.99, lambda_: float = 0.95, normalize: bool = True) -> PpoBatch:
+    """The PPO notebook's "PHASE 2" over one rollout (each lane's first episode).
+
+    ``obs [T, N, 15]`` float32, ``actions [T, N]`` uint8 bitmasks and
+    ``log_prob [T, N]`` float32 (either may be ``None``, its output is then
+    ``None``), ``reward [T, N]`` float32 or float64, ``done [T, N]`` bool or
+    uint8: contiguous, on one GPU.  ``critic`` maps ``[rows, 15]`` to one
+    value per row (an :class:`~delivery_drone_amd.MlpNet` with ``out_dim ==
+    1``); it runs on the ``M`` gathered rows, and on ``bootstrap_obs [N, 15]``
+    (the observation after the last frame, ``env.obs``; default: bootstrap 0)
+    for the episodes that did not end.  ``normalize=False`` leaves
+    ``advantages`` raw (``adv_mean`` / ``adv_std`` are still returned, so
+    that several ranks can combine their statistics).  ``M < 2``: NaN.
+    """
+    plan = _Plan(done)
+    if obs is None:
+        raise ValueError("ppo_batch needs obs: the critic runs on the gathered states")
+    states, acts, lps = plan.gather(obs, actions, log_prob)
+    values = _values(critic, states, "states")
+    bootstrap = None
+    if bootstrap_obs is not None:
+        b = _rollout_buffer(bootstrap_obs, (plan.n, abi.DD_OBS_DIM), torch.float32, plan.dev, "bootstrap_obs")
+        bootstrap = _values(critic, b, "bootstrap_obs")
+    raw, ret, ep = plan.advantages(reward, abi.DD_BATCH_GAE, gamma, lambda_, values=values, bootstrap=bootstrap)
+    mean, std, adv = plan.normalize(raw, normalize)
+    return PpoBatch(states, acts, lps, adv, ret, values, plan.lengths, plan.offsets, plan.ended.view(torch.bool), ep,
+                    mean, std)
+
+
+def reinforce_batch(obs: Optional[torch.Tensor], actions: Optional[torch.Tensor], reward: torch.Tensor,
+                    done: torch.Tensor, gamma: float = 0.99, normalize: bool = True) -> ReinforceBatch:
+    """The REINFORCE notebook's batch: ``compute_returns`` per episode (double,
+    rounded to float32 once), ``baseline`` = their mean, ``advantages`` =
+    ``(returns - baseline) / (std + 1e-8)`` (the notebook's baseline
+    subtraction followed by its normalisation; ``normalize=False``: the
+    returns themselves).  Buffers as :func:`ppo_batch`; ``obs`` and
+    ``actions`` are optional."""
+    plan = _Plan(done)
+    states, acts, _ = plan.gather(obs, actions, None)
+    _, ret, ep = plan.advantages(reward, abi.DD_BATCH_RETURNS, gamma)
+    mean, std, adv = plan.normalize(ret, normalize)
+    return ReinforceBatch(states, acts, ret, adv, mean, std, plan.lengths, plan.offsets,
+                          plan.ended.view(torch.bool), ep)
+
+
+def collect_ppo(env, actor, critic, max_steps: int = 300, seed: int = 0, step: int = 0, gamma: float = 0.99,
+                lambda_: float = 0.95, normalize: bool = True) -> PpoBatch:
+    """One PPO iteration's data: ``env.reset()``, ``env.policy_rollout(actor,
+    max_steps, seed=seed, step=step)`` (``collect_episodes_ppo``), then
+    :func:`ppo_batch` with ``env.obs`` as the bootstrap state."""
+    env.reset()
+    obs, acts, lp, reward, done = env.policy_rollout(actor, int(max_steps), seed=seed, step=step)
+    return ppo_batch(obs, acts, lp, reward, done, critic, bootstrap_obs=env.obs, gamma=gamma, lambda_=lambda_,
+                     normalize=normalize)
