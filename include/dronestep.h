@@ -645,6 +645,77 @@ int dd_batch_advantages(const DDBatchLayout *layout, const DDBatchAdvIO *io, int
 int dd_batch_normalize(const float *x, float *out, int64_t m, double *mean, double *std,
                        void *workspace, void *stream);
 
+/* ---- Training batches of every episode of a rollout ----------------------
+ * The stages above keep each lane's first episode, as collect_episodes_ppo
+ * plays one episode per game.  These keep every episode of the same [T][N]
+ * buffers: a fixed-length rollout of an auto_reset env, continued from one
+ * PPO iteration to the next (the notebook's "rollout_steps ... steps to
+ * collect before update"), then uses every frame but the one re-spawn frame
+ * per episode.  The rule is done's alone:
+ *   - frame t of lane i is DROPPED when the frame before it was done:
+ *     done[t-1][i] != 0, or for t = 0 done_before[i] != 0 (done_before uint8
+ *     [N]: the env's done flags before the rollout; null = all zero).  On an
+ *     auto-reset env that is exactly the re-spawn frame (DDConfig.auto_reset:
+ *     terminal observation in, action ignored, reward 0, not done); on a
+ *     sticky-done env every frame after the first done, so there the batch
+ *     is the first-episode batch above.
+ *   - an EPISODE is a maximal run of kept frames of one lane: frames
+ *     [ep_start, ep_start + ep_length), consecutive because a dropped frame
+ *     only follows a done.  It is ended (ep_ended = 1) when its last frame is
+ *     done, else open: cut by the end of the rollout, the lane's last, at most
+ *     one per lane.  With done_before[i] == 0 a lane's first episode continues
+ *     what the lane was doing before the rollout; it is an ordinary episode.
+ *   - order: lanes ascending, a lane's episodes in time order, so a lane's
+ *     rows are its kept frames in frame order:
+ *     row(i, t) = lane_row[i] + (kept frames of lane i before t).
+ * DD_EPISODES_DROP_OPEN (count and fill) leaves open episodes out of the
+ * batch, frames and records: a discounted return cut by the rollout's end is
+ * no return (REINFORCE).  An episode that began before the rollout and ends
+ * in it stays: its G_t depend on later rewards only.
+ *
+ * DDEpisodeLayout (caller-owned, device): lane_episode / lane_row, the
+ * exclusive prefix sums over lanes of the episode and row counts, [N] = E and
+ * M; per episode its lane, first frame, length, ended flag and first row
+ * (ep_offset[E] = M).
+ *
+ * dd_episodes_count writes lane_episode and lane_row (one thread per lane
+ * walks its T flags; deterministic fixed-shape scan, no atomics) and E, M
+ * also to totals (device, 16 bytes), which the host reads once to size the
+ * rest.  workspace: dd_episodes_workspace(n) bytes, 8-byte aligned.  T == 0 or
+ * n == 0: all zero.  dd_episodes_fill writes the five per-episode arrays
+ * (same flags as the count).  dd_episodes_gather is dd_batch_gather for this
+ * layout (same DDBatchGatherIO, same LDS tiles; it reads lane_row only, and
+ * recomputes a lane's kept-frame rank at a tile's first frame from done, so it
+ * needs done and done_before again; frames of a dropped open episode are
+ * those whose rank is not below the lane's row count).  No row >= M and
+ * nothing for a dropped frame is written.  dd_episodes_advantages is
+ * dd_batch_advantages per episode (same DDBatchAdvIO and arithmetic):
+ * episode_return double [E], bootstrap float [N] used after an open episode's
+ * last frame (bootstrap[ep_lane]; null = 0; 0 after an ended one).  The
+ * normalisation is dd_batch_normalize on the M rows.  Errors as above: a null
+ * required pointer, negative T or n, an unknown flag, mode or precision, an
+ * input without its output: hipErrorInvalidValue before any launch. */
+typedef struct DDEpisodeLayout {
+    int64_t *lane_episode;   /* [N+1], [N] = E */
+    int64_t *lane_row;       /* [N+1], [N] = M */
+    int32_t *ep_lane;        /* [E]   (the ep_ fields may be null for dd_episodes_count and _gather) */
+    int32_t *ep_start;       /* [E]   */
+    int32_t *ep_length;      /* [E]   */
+    uint8_t *ep_ended;       /* [E]   */
+    int64_t *ep_offset;      /* [E+1] */
+} DDEpisodeLayout;
+#define DD_EPISODES_DROP_OPEN 1
+
+int64_t dd_episodes_workspace(int64_t n);
+int dd_episodes_count(const uint8_t *done, const uint8_t *done_before, int64_t T, int64_t n, int32_t flags,
+                      const DDEpisodeLayout *layout, int64_t *totals, void *workspace, void *stream);
+int dd_episodes_fill(const uint8_t *done, const uint8_t *done_before, int64_t T, int64_t n, int32_t flags,
+                     const DDEpisodeLayout *layout, void *stream);
+int dd_episodes_gather(const DDEpisodeLayout *layout, const uint8_t *done, const uint8_t *done_before,
+                       const DDBatchGatherIO *io, int64_t T, int64_t n, void *stream);
+int dd_episodes_advantages(const DDEpisodeLayout *layout, const DDBatchAdvIO *io, int64_t T, int64_t n,
+                           void *stream);
+
 #ifdef __cplusplus
 }
 #endif

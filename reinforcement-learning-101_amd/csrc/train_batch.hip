@@ -16,34 +16,13 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "batch_core.h"
 #include "dronestep.h"
 #include "gae_core.h"
 #include "lane_io.h"
 #include "launch.h"
 
 namespace dd {
-
-constexpr int kGatherLanes = 64;                       // lanes of one gather tile: one frame's rows are 3,840 contiguous bytes
-constexpr int kObsRow = kGatherLanes * DD_OBS_DIM;     // floats of one frame of a tile
-constexpr int kObsRowPad = kObsRow + 4;                // + room for the source's 16-byte phase
-constexpr int kStatBlocks = 512;                       // partial sums of the statistics: fixed, so the tree is
-constexpr int kScanBlock = 1024;
-
-// Sum over the block in a fixed tree (same bits on every run); every thread
-// gets the result.  sh: kBlock elements, free again on return.
-template <typename V>
-__device__ __forceinline__ V block_sum(V v, V* sh) {
-    sh[threadIdx.x] = v;
-    __syncthreads();
-#pragma unroll
-    for (int half = kBlock / 2; half > 0; half >>= 1) {
-        if (threadIdx.x < (unsigned)half) sh[threadIdx.x] += sh[threadIdx.x + half];
-        __syncthreads();
-    }
-    const V total = sh[0];
-    __syncthreads();
-    return total;
-}
 
 // ---------------------------------------------------------------------------
 // Plan.  length: one thread per lane reads its column of done[T][N] forward,
@@ -135,10 +114,6 @@ __global__ __launch_bounds__(kBlock) void batch_offset_kernel(const int32_t* __r
 // lanes past an episode's end are neither read nor written, and a tile with no
 // live frame returns after reading its 64 lengths.
 // ---------------------------------------------------------------------------
-__device__ __forceinline__ int obs_phase(const float* obs, int64_t first_elem) {
-    return (int)((((uintptr_t)obs >> 2) + (uint64_t)first_elem) & 3);
-}
-
 template <int F>
 __global__ __launch_bounds__(kBlock) void batch_gather_kernel(const int32_t* __restrict__ length,
                                                               const int64_t* __restrict__ offset,

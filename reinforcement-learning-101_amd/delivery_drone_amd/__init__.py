@@ -10,7 +10,10 @@ for on-device collection, and the notebooks' ``evaluate_policy`` (temperature
 or greedy action selection, one episode per lane:
 :meth:`VecDroneEnv.evaluate_policy`); and the notebooks' training batches
 built from rollout buffers on device (:func:`ppo_batch`,
-:func:`reinforce_batch`, :func:`collect_ppo`).
+:func:`reinforce_batch`, :func:`collect_ppo`), from each lane's first
+episode or from every episode of an auto-reset rollout
+(:func:`ppo_episodes_batch`, :func:`reinforce_episodes_batch`,
+:func:`collect_ppo_steps`).
 """
 from .config import EnvConfig
 from .vec_env import OBS_KEYS, StepInfo, VecDroneEnv
@@ -19,11 +22,13 @@ from .sharding import dist_env, gather_obs, shard_bounds
 from .gae import gae
 from .policy import MlpNet
 from .train_batch import collect_ppo, ppo_batch, reinforce_batch
+from .train_batch import collect_ppo_steps, ppo_episodes_batch, reinforce_episodes_batch
 
 __all__ = [
     "EnvConfig", "VecDroneEnv", "StepInfo", "OBS_KEYS",
     "DroneGame", "DroneGameClient", "DroneState", "action_bits",
     "shard_bounds", "dist_env", "gather_obs", "gae", "MlpNet",
     "ppo_batch", "reinforce_batch", "collect_ppo",
+    "ppo_episodes_batch", "reinforce_episodes_batch", "collect_ppo_steps",
 ]
 __version__ = "0.1.0"

@@ -21,6 +21,7 @@ __all__ = [
     "DD_SAMPLE_BERNOULLI", "DD_SAMPLE_TEMPERED", "DD_SAMPLE_GREEDY",
     "DDConfig", "DDState", "DDStepIO", "DDRolloutIO", "DDMlpParams", "DDMlpIO", "DDPolicyRolloutIO", "DDSampling",
     "DDEpisodeStats", "DD_BATCH_GAE", "DD_BATCH_RETURNS", "DDBatchLayout", "DDBatchGatherIO", "DDBatchAdvIO",
+    "DD_EPISODES_DROP_OPEN", "DDEpisodeLayout",
     "sampling_mode", "lib", "load", "library_path", "check",
     "NativeLibraryError",
 ]
@@ -39,6 +40,7 @@ DD_ERR_HANDOVER = 1
 DD_MEM_DEFAULT, DD_MEM_CONTIGUOUS = 0, 1
 DD_SAMPLE_BERNOULLI, DD_SAMPLE_TEMPERED, DD_SAMPLE_GREEDY = 0, 1, 2
 DD_BATCH_GAE, DD_BATCH_RETURNS = 0, 1
+DD_EPISODES_DROP_OPEN = 1
 
 _D = ctypes.c_double
 _I = ctypes.c_int32
@@ -155,6 +157,12 @@ class DDBatchAdvIO(ctypes.Structure):
                 ("episode_return", ctypes.c_void_p), ("gamma", _D), ("lambda_", _D)]
 
 
+class DDEpisodeLayout(ctypes.Structure):
+    _fields_ = [("lane_episode", ctypes.c_void_p), ("lane_row", ctypes.c_void_p), ("ep_lane", ctypes.c_void_p),
+                ("ep_start", ctypes.c_void_p), ("ep_length", ctypes.c_void_p), ("ep_ended", ctypes.c_void_p),
+                ("ep_offset", ctypes.c_void_p)]
+
+
 def sampling_mode(temperature) -> int:
     """The ``DD_SAMPLE_*`` mode of a notebook ``temperature``: 1 is the plain
     Bernoulli draw, 0 greedy (``probs > 0.5``), any other positive finite value
@@ -225,6 +233,17 @@ EXPORTS = {
                                            ctypes.c_int64, ctypes.c_int64, ctypes.c_void_p]),
     "dd_batch_normalize": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p,
                                           ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+    "dd_episodes_workspace": (ctypes.c_int64, [ctypes.c_int64]),
+    "dd_episodes_count": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, _I,
+                                         ctypes.POINTER(DDEpisodeLayout), ctypes.c_void_p, ctypes.c_void_p,
+                                         ctypes.c_void_p]),
+    "dd_episodes_fill": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, _I,
+                                        ctypes.POINTER(DDEpisodeLayout), ctypes.c_void_p]),
+    "dd_episodes_gather": (ctypes.c_int, [ctypes.POINTER(DDEpisodeLayout), ctypes.c_void_p, ctypes.c_void_p,
+                                          ctypes.POINTER(DDBatchGatherIO), ctypes.c_int64, ctypes.c_int64,
+                                          ctypes.c_void_p]),
+    "dd_episodes_advantages": (ctypes.c_int, [ctypes.POINTER(DDEpisodeLayout), ctypes.POINTER(DDBatchAdvIO),
+                                              ctypes.c_int64, ctypes.c_int64, ctypes.c_void_p]),
 }
 
 #: symbols a timing-only lab build (tools/build_variants.sh) or an older
@@ -232,7 +251,8 @@ EXPORTS = {
 _LAB_OPTIONAL = ("dd_build_info", "dd_selftest_sqrt", "dd_rollout_kernel", "dd_device_errors", "dd_stamp",
                  "dd_wall_clock_khz", "dd_device_alloc", "dd_device_free", "dd_mlp_forward_sampled",
                  "dd_policy_rollout_sampled", "dd_batch_workspace", "dd_batch_plan", "dd_batch_gather",
-                 "dd_batch_advantages", "dd_batch_normalize")
+                 "dd_batch_advantages", "dd_batch_normalize", "dd_episodes_workspace", "dd_episodes_count",
+                 "dd_episodes_fill", "dd_episodes_gather", "dd_episodes_advantages")
 
 
 class NativeLibraryError(RuntimeError):

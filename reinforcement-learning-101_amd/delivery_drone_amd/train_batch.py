@@ -33,7 +33,9 @@ import torch
 
 from . import abi
 
-__all__ = ["PpoBatch", "ReinforceBatch", "ppo_batch", "reinforce_batch", "collect_ppo"]
+__all__ = ["PpoBatch", "ReinforceBatch", "ppo_batch", "reinforce_batch", "collect_ppo",
+           "PpoEpisodesBatch", "ReinforceEpisodesBatch", "ppo_episodes_batch", "reinforce_episodes_batch",
+           "collect_ppo_steps"]
 
 
 class PpoBatch(NamedTuple):
@@ -219,3 +221,204 @@ def collect_ppo(env, actor, critic, max_steps: int = 300, seed: int = 0, step: i
     obs, acts, lp, reward, done = env.policy_rollout(actor, int(max_steps), seed=seed, step=step)
     return ppo_batch(obs, acts, lp, reward, done, critic, bootstrap_obs=env.obs, gamma=gamma, lambda_=lambda_,
                      normalize=normalize)
+
+
+# ---- every episode of a rollout (csrc/train_batch_episodes.hip) --------------
+#
+# The stages above keep each lane's first episode.  On an ``auto_reset=True``
+# env the later episodes are in the same ``[frames, N]`` buffers; the functions
+# below batch all of them.  ``done`` alone decides (include/dronestep.h): frame
+# ``t`` of a lane is dropped when the frame before it was done (``done[t - 1]``,
+# or ``done_before`` for ``t == 0``): the re-spawn frame of an auto-reset env,
+# every later frame of a sticky one.  An episode is a maximal run of kept
+# frames; it is *ended* when its last frame is done, else *open* (cut by the end
+# of the rollout; the lane's last).  Lanes ascend and a lane's episodes are in
+# time order, so a lane's rows are its kept frames in frame order.
+
+class PpoEpisodesBatch(NamedTuple):
+    states: Optional[torch.Tensor]         # [M, 15]
+    actions: Optional[torch.Tensor]        # [M, 3] float32, 1.0 / 0.0 (main, left, right)
+    old_log_probs: Optional[torch.Tensor]  # [M]
+    advantages: torch.Tensor               # [M], normalised unless normalize=False
+    returns: torch.Tensor                  # [M] = raw advantages + values
+    values: torch.Tensor                   # [M], the critic on states
+    ep_lane: torch.Tensor                  # [E] int32
+    ep_start: torch.Tensor                 # [E] int32, the frame of the episode's first row
+    ep_lengths: torch.Tensor               # [E] int32
+    ep_offsets: torch.Tensor               # [E + 1] int64, ep_offsets[E] = M
+    ep_ended: torch.Tensor                 # [E] bool
+    episode_return: torch.Tensor           # [E] float64, sum(rewards)
+    lane_episode_offsets: torch.Tensor     # [N + 1] int64: lane i's episodes are [o[i], o[i + 1])
+    lane_row_offsets: torch.Tensor         # [N + 1] int64: and its rows
+    adv_mean: torch.Tensor                 # 0-d float64, of the raw advantages
+    adv_std: torch.Tensor                  # 0-d float64, unbiased
+
+
+class ReinforceEpisodesBatch(NamedTuple):
+    states: Optional[torch.Tensor]
+    actions: Optional[torch.Tensor]
+    returns: torch.Tensor                  # [M] discounted returns, float32
+    advantages: torch.Tensor               # [M] (returns - baseline) / (std + 1e-8); returns with normalize=False
+    baseline: torch.Tensor                 # 0-d float64, mean of returns
+    std: torch.Tensor                      # 0-d float64, unbiased
+    ep_lane: torch.Tensor
+    ep_start: torch.Tensor
+    ep_lengths: torch.Tensor
+    ep_offsets: torch.Tensor
+    ep_ended: torch.Tensor
+    episode_return: torch.Tensor
+    lane_episode_offsets: torch.Tensor
+    lane_row_offsets: torch.Tensor
+
+
+class _EpisodePlan:
+    """The episode layout of one rollout and what the later stages need of it."""
+
+    def __init__(self, done: torch.Tensor, done_before: Optional[torch.Tensor] = None, drop_open: bool = False):
+        if not isinstance(done, torch.Tensor) or done.dim() != 2:
+            raise ValueError("done must be [T, N]")
+        if done.device.type != "cuda":
+            raise ValueError("training batches are built on the GPU; move the rollout to a CUDA/HIP device")
+        if done.dtype not in (torch.bool, torch.uint8):
+            raise ValueError(f"done must be bool or uint8, got {done.dtype}")
+        if not done.is_contiguous():
+            raise ValueError("done must be contiguous")
+        self.T, self.n = T, n = int(done.shape[0]), int(done.shape[1])
+        self.dev = dev = done.device
+        self.done = done.view(torch.uint8) if done.dtype == torch.bool else done
+        self.done_before = _rollout_buffer(done_before, (n,), torch.uint8, dev, "done_before")
+        self.flags = abi.DD_EPISODES_DROP_OPEN if drop_open else 0
+        self.lib = lib = abi.lib()
+        self.lane_episode = torch.empty(n + 1, dtype=torch.int64, device=dev)
+        self.lane_row = torch.empty(n + 1, dtype=torch.int64, device=dev)
+        totals = torch.empty(2, dtype=torch.int64, device=dev)
+        size = max(int(lib.dd_episodes_workspace(n)), int(lib.dd_batch_workspace(n)))
+        self.workspace = torch.empty(size // 8, dtype=torch.int64, device=dev)
+        self.layout = abi.DDEpisodeLayout(self.lane_episode.data_ptr(), self.lane_row.data_ptr())
+        abi.check(lib.dd_episodes_count(_ptr(self.done), _ptr(self.done_before), T, n, self.flags,
+                                        ctypes.byref(self.layout), totals.data_ptr(), self.workspace.data_ptr(),
+                                        _stream(dev)), "dd_episodes_count")
+        self.E, self.M = E, M = tuple(int(v) for v in totals.tolist())  # the one synchronisation: the flat tensors' size
+        self.ep_lane = torch.empty(E, dtype=torch.int32, device=dev)
+        self.ep_start = torch.empty(E, dtype=torch.int32, device=dev)
+        self.ep_length = torch.empty(E, dtype=torch.int32, device=dev)
+        self.ep_ended = torch.empty(E, dtype=torch.uint8, device=dev)
+        self.ep_offset = torch.zeros(1, dtype=torch.int64, device=dev) if E == 0 else \
+            torch.empty(E + 1, dtype=torch.int64, device=dev)
+        if E > 0:  # an empty tensor has no address to pass
+            self.layout = abi.DDEpisodeLayout(self.lane_episode.data_ptr(), self.lane_row.data_ptr(),
+                                              self.ep_lane.data_ptr(), self.ep_start.data_ptr(),
+                                              self.ep_length.data_ptr(), self.ep_ended.data_ptr(),
+                                              self.ep_offset.data_ptr())
+            abi.check(lib.dd_episodes_fill(self.done.data_ptr(), _ptr(self.done_before), T, n, self.flags,
+                                           ctypes.byref(self.layout), _stream(dev)), "dd_episodes_fill")
+
+    def gather(self, obs, actions, log_prob, tile_frames: int = 0):
+        T, n, dev, M = self.T, self.n, self.dev, self.M
+        obs = _rollout_buffer(obs, (T, n, abi.DD_OBS_DIM), torch.float32, dev, "obs")
+        actions = _rollout_buffer(actions, (T, n), torch.uint8, dev, "actions")
+        log_prob = _rollout_buffer(log_prob, (T, n), torch.float32, dev, "log_prob")
+        states = torch.empty(M, abi.DD_OBS_DIM, dtype=torch.float32, device=dev) if obs is not None else None
+        acts = torch.empty(M, 3, dtype=torch.float32, device=dev) if actions is not None else None
+        lps = torch.empty(M, dtype=torch.float32, device=dev) if log_prob is not None else None
+        if M > 0:
+            io = abi.DDBatchGatherIO(_ptr(obs), _ptr(actions), _ptr(log_prob), _ptr(states), _ptr(acts), _ptr(lps),
+                                     int(tile_frames), 0)
+            abi.check(self.lib.dd_episodes_gather(ctypes.byref(self.layout), self.done.data_ptr(),
+                                                  _ptr(self.done_before), ctypes.byref(io), T, n, _stream(dev)),
+                      "dd_episodes_gather")
+        return states, acts, lps
+
+    def advantages(self, reward, mode, gamma, lambda_=0.0, values=None, bootstrap=None):
+        T, n, dev, M, E = self.T, self.n, self.dev, self.M, self.E
+        if not isinstance(reward, torch.Tensor) or reward.dtype not in (torch.float32, torch.float64):
+            raise ValueError("reward must be a float32 or float64 tensor")
+        reward = _rollout_buffer(reward, (T, n), reward.dtype, dev, "reward")
+        adv = torch.empty(M, dtype=torch.float32, device=dev) if mode == abi.DD_BATCH_GAE else None
+        ret = torch.empty(M, dtype=torch.float32, device=dev)
+        ep = torch.empty(E, dtype=torch.float64, device=dev)
+        if M > 0:
+            io = abi.DDBatchAdvIO(reward.data_ptr(), abi.DD_F64 if reward.dtype == torch.float64 else abi.DD_F32,
+                                  mode, _ptr(values), _ptr(bootstrap), _ptr(adv), ret.data_ptr(), ep.data_ptr(),
+                                  float(gamma), float(lambda_))
+            abi.check(self.lib.dd_episodes_advantages(ctypes.byref(self.layout), ctypes.byref(io), T, n,
+                                                      _stream(dev)), "dd_episodes_advantages")
+        return adv, ret, ep
+
+    def normalize(self, x: torch.Tensor, normalize: bool):
+        """(mean, std, normalised x or x itself)."""
+        stats = torch.empty(2, dtype=torch.float64, device=self.dev)
+        out = torch.empty_like(x) if normalize else None
+        abi.check(self.lib.dd_batch_normalize(_ptr(x) if self.M else None, _ptr(out) if self.M else None, self.M,
+                                              stats[0:].data_ptr(), stats[1:].data_ptr(),
+                                              self.workspace.data_ptr(), _stream(self.dev)), "dd_batch_normalize")
+        return stats[0], stats[1], out if normalize else x
+
+    def records(self):
+        return (self.ep_lane, self.ep_start, self.ep_length, self.ep_offset, self.ep_ended.view(torch.bool))
+
+
+def ppo_episodes_batch(obs: torch.Tensor, actions: Optional[torch.Tensor], log_prob: Optional[torch.Tensor],
+                       reward: torch.Tensor, done: torch.Tensor, critic,
+                       bootstrap_obs: Optional[torch.Tensor] = None, done_before: Optional[torch.Tensor] = None,
+                       gamma: float = 0.99, lambda_: float = 0.95, normalize: bool = True) -> PpoEpisodesBatch:
+    """The PPO notebook's "PHASE 2" over every episode of one rollout.
+
+    Buffers as :func:`ppo_batch` (checked, never copied).  ``done_before [N]``
+    bool or uint8: the lanes' done flags before the rollout (default: none
+    done); a lane that was done spends frame 0 re-spawning, which is no row.
+    ``critic`` runs on the ``M`` gathered rows and on ``bootstrap_obs [N, 15]``
+    (``env.obs`` after the rollout; default: bootstrap 0), whose value follows
+    the last frame of a lane's open episode; an ended episode bootstraps 0, as
+    the training cell's ``dones[-1] = True``.  With no row at all (``M == 0``)
+    every flat tensor is empty and the statistics are NaN, as ``M < 2`` gives.
+    """
+    plan = _EpisodePlan(done, done_before)
+    if obs is None:
+        raise ValueError("ppo_episodes_batch needs obs: the critic runs on the gathered states")
+    states, acts, lps = plan.gather(obs, actions, log_prob)
+    values = _values(critic, states, "states") if plan.M > 0 else states.new_empty(0)
+    bootstrap = None
+    if bootstrap_obs is not None:
+        b = _rollout_buffer(bootstrap_obs, (plan.n, abi.DD_OBS_DIM), torch.float32, plan.dev, "bootstrap_obs")
+        bootstrap = _values(critic, b, "bootstrap_obs") if plan.n > 0 else None
+    raw, ret, ep = plan.advantages(reward, abi.DD_BATCH_GAE, gamma, lambda_, values=values, bootstrap=bootstrap)
+    mean, std, adv = plan.normalize(raw, normalize)
+    return PpoEpisodesBatch(states, acts, lps, adv, ret, values, *plan.records(), ep, plan.lane_episode,
+                            plan.lane_row, mean, std)
+
+
+def reinforce_episodes_batch(obs: Optional[torch.Tensor], actions: Optional[torch.Tensor], reward: torch.Tensor,
+                             done: torch.Tensor, done_before: Optional[torch.Tensor] = None, gamma: float = 0.99,
+                             normalize: bool = True, drop_open: bool = True) -> ReinforceEpisodesBatch:
+    """The REINFORCE notebook's batch over every episode of one rollout:
+    ``compute_returns`` per episode, then the baseline and the normalisation as
+    :func:`reinforce_batch`.  ``drop_open`` (default) leaves the episodes that
+    the end of the rollout cut out of the batch, rows and records: a
+    discounted return that misses its later rewards is no return.  An episode
+    that began before the rollout and ends in it stays."""
+    plan = _EpisodePlan(done, done_before, drop_open=bool(drop_open))
+    states, acts, _ = plan.gather(obs, actions, None)
+    _, ret, ep = plan.advantages(reward, abi.DD_BATCH_RETURNS, gamma)
+    mean, std, adv = plan.normalize(ret, normalize)
+    return ReinforceEpisodesBatch(states, acts, ret, adv, mean, std, *plan.records(), ep, plan.lane_episode,
+                                  plan.lane_row)
+
+
+def collect_ppo_steps(env, actor, critic, frames: int, seed: int = 0, step: int = 0, gamma: float = 0.99,
+                      lambda_: float = 0.95, normalize: bool = True) -> PpoEpisodesBatch:
+    """``frames`` more frames of an ``auto_reset=True`` env as one PPO batch:
+    the fixed-horizon collection (the notebook's ``rollout_steps``).  Does
+    *not* reset the env: called in a loop with ``step`` advanced by ``frames``,
+    each call continues the lanes' running episodes (their first rows) and
+    bootstraps the ones it cuts from ``env.obs``.  The lanes that are done when
+    the call starts re-spawn in frame 0; they are read from the env's status
+    (``DD_ST_DONE``: what the kernels re-spawn by, and, unlike ``env.done``,
+    kept current by ``policy_rollout``)."""
+    if not env.config.auto_reset:
+        raise ValueError("collect_ppo_steps batches every episode of a rollout that re-spawns its lanes: the env "
+                         "needs auto_reset=True (collect_ppo plays one episode per lane on a sticky-done env)")
+    done_before = (env.status & abi.DD_ST_DONE).ne(0).to(torch.uint8)
+    obs, acts, lp, reward, done = env.policy_rollout(actor, int(frames), seed=seed, step=step)
+    return ppo_episodes_batch(obs, acts, lp, reward, done, critic, bootstrap_obs=env.obs, done_before=done_before,
+                              gamma=gamma, lambda_=lambda_, normalize=normalize)
