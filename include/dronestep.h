@@ -413,6 +413,41 @@ int dd_mlp_forward_sampled(const float *packed, int32_t compute, int32_t out_dim
                            const DDMlpIO *io, const DDSampling *sampling, int64_t n,
                            void *stream);
 
+/* ---- Scoring given actions (compute_ppo_losses' first lines) ---------------
+ * compute_ppo_losses (Actor_Critic_PPO.ipynb, the cell after
+ * collect_episodes_ppo) re-evaluates the actor on the batch's states and
+ * scores the actions that were taken:
+ *   dist = Bernoulli(probs=policy(states))
+ *   new_log_probs = dist.log_prob(actions).sum(dim=1);  dist.entropy()
+ * dd_mlp_evaluate_actions is dd_mlp_forward's actor (K = 3, either compute)
+ * with the action an input instead of a draw.  actions: DD_ACT_BITMASK, uint8
+ * [n], bits 0-2 as dd_step reads them; or DD_ACT_F32X3, float [n][3] (main,
+ * left, right), where a float is "on" by dd_step's rule for that format:
+ * nonzero = on (a != 0.0f, so -0.0 is off and NaN is on).
+ * log_prob: dd_mlp_forward's own arithmetic (each factor p or 1 - p on the
+ * probability clamped to [FLT_EPSILON, 1 - FLT_EPSILON], one logf of the
+ * three factors' product), so for the actions dd_mlp_forward drew on the same
+ * rows it is bit-equal to the log_prob that call wrote.  entropy: the row's
+ * sum over its three factors of -(pc log pc + (1 - pc) log(1 - pc)) on the
+ * same clamped pc, Bernoulli(probs=p).entropy().  A buffer packed for the
+ * other compute or for K = 1 gives NaN probabilities, log_prob and entropy.
+ * hipErrorInvalidValue, before any HIP call: a null io, n < 0, an unknown
+ * format or compute; and with n > 0 a null or misaligned packed pointer, null
+ * obs or null actions.  n == 0 is success. */
+typedef struct DDMlpEvalIO {
+    const float *obs;      /* [n][15] f32                                        */
+    const void *actions;   /* by action_format (required)                        */
+    int32_t action_format; /* DD_ACT_BITMASK or DD_ACT_F32X3                     */
+    int32_t _pad;
+    float *probs;          /* nullable: [n][3] Sigmoid probabilities             */
+    float *log_prob;       /* nullable: [n] summed log-probability of `actions`  */
+    float *entropy;        /* nullable: [n] the three factors' entropies, summed */
+    int64_t n;
+} DDMlpEvalIO;
+
+int dd_mlp_evaluate_actions(const float *packed, int32_t compute, const DDMlpEvalIO *io,
+                            void *stream);
+
 /* ---- The collection loop with the actor in it --
  * collect_episodes_ppo (Actor_Critic_PPO.ipynb:797-917) for N drones and
  * `frames` frames in one launch: per frame, the actor on the current
@@ -715,6 +750,74 @@ int dd_episodes_gather(const DDEpisodeLayout *layout, const uint8_t *done, const
                        const DDBatchGatherIO *io, int64_t T, int64_t n, void *stream);
 int dd_episodes_advantages(const DDEpisodeLayout *layout, const DDBatchAdvIO *io, int64_t T, int64_t n,
                            void *stream);
+
+/* ---- PPO losses and head gradients (compute_ppo_losses, the rest) ---------
+ * From the per-row outputs of dd_mlp_evaluate_actions (log_prob, entropy,
+ * probs) and of dd_mlp_forward on the critic (values), with the batch's
+ * old_log_prob, advantages and returns, all float [m]:
+ *   r           = exp(log_prob - old_log_prob)      the difference in float32,
+ *                 exp in double, rounded to float32 once
+ *   policy_loss = -mean(min(r A, clip(r, 1 - eps, 1 + eps) A))
+ *   value_loss  = mean((v - R)^2)
+ *   entropy     = sum(row entropy) / (3 m)          dist.entropy().mean()
+ *   total_loss  = policy_loss + value_coef value_loss - entropy_coef entropy
+ *   ratio_mean, ratio_min, ratio_max, ratio_std (unbiased: NaN at m == 1, as
+ *   torch.std), clipped_frac = share of rows with r < 1 - eps or r > 1 + eps
+ * into result[DD_PPO_*] (device doubles).  The clip bounds are float32(1 -
+ * eps) and float32(1 + eps), as torch compares a float32 tensor with a Python
+ * number; products and sums are in double (a product of two floats is exact
+ * there), the sums over a reduction tree of fixed shape (no atomics: the same
+ * bits on every run and every device), the std by a second pass over the
+ * deviations from the mean.  Optional per-row outputs: ratio [m], and the
+ * gradient of total_loss at the two networks' outputs, what torch autograd
+ * leaves there:
+ *   grad_values[i]    = value_coef 2 (v_i - R_i) / m
+ *   grad_logits[i][k] = g_i (a_ik - p_ik)
+ *                       + entropy_coef / (3 m) logit(p_ik) p_ik (1 - p_ik)
+ *   g_i = -A_i r_i / m  where r_i A_i < clip(r_i) A_i or 1 - eps <= r_i <= 1 + eps,
+ *         else 0;  a factor whose p lies outside [FLT_EPSILON, 1 - FLT_EPSILON]
+ *         contributes 0 (clamp_probs passes no gradient there)
+ * at the actor's pre-Sigmoid outputs and the critic's value (the derivation
+ * is csrc/ppo_loss.hip's header).  grad_logits needs probs and actions
+ * (action_format as DDMlpEvalIO); without it both may be NULL.  workspace:
+ * dd_ppo_loss_workspace() bytes, 8-byte aligned.  hipErrorInvalidValue, before
+ * any HIP call: a null io, m <= 0 (a mean over no rows has no value), a null
+ * required pointer, a clip_epsilon that is negative or not finite, an unknown
+ * action_format.  All indices are 64-bit. */
+enum {
+    DD_PPO_TOTAL_LOSS = 0,
+    DD_PPO_POLICY_LOSS = 1,
+    DD_PPO_VALUE_LOSS = 2,
+    DD_PPO_ENTROPY = 3,
+    DD_PPO_RATIO_MEAN = 4,
+    DD_PPO_RATIO_MIN = 5,
+    DD_PPO_RATIO_MAX = 6,
+    DD_PPO_RATIO_STD = 7,
+    DD_PPO_CLIPPED_FRAC = 8,
+    DD_PPO_RESULTS = 9
+};
+typedef struct DDPpoLossIO {
+    const float *log_prob;     /* [m]                                            */
+    const float *entropy;      /* [m] row sums over the three factors            */
+    const float *probs;        /* [m][3]; required with grad_logits              */
+    const float *values;       /* [m]                                            */
+    const float *old_log_prob; /* [m]                                            */
+    const float *advantages;   /* [m]                                            */
+    const float *returns;      /* [m]                                            */
+    const void *actions;       /* by action_format; required with grad_logits    */
+    int32_t action_format;     /* DD_ACT_BITMASK or DD_ACT_F32X3                 */
+    int32_t _pad;
+    double clip_epsilon;
+    double entropy_coef;
+    double value_coef;
+    double *result;            /* [DD_PPO_RESULTS]                               */
+    float *ratio;              /* nullable [m]                                   */
+    float *grad_logits;        /* nullable [m][3]                                */
+    float *grad_values;        /* nullable [m]                                   */
+} DDPpoLossIO;
+
+int64_t dd_ppo_loss_workspace(void);
+int dd_ppo_losses(const DDPpoLossIO *io, int64_t m, void *workspace, void *stream);
 
 #ifdef __cplusplus
 }

@@ -523,6 +523,33 @@ __device__ __forceinline__ void actor_sample(const float (&prob)[3], uint64_t en
     lp = fmaf(prob[0] + prob[1] + prob[2], 0.0f, lp);
 }
 
+// compute_ppo_losses' scoring of a given action (Actor_Critic_PPO.ipynb, the
+// cell after collect_episodes_ppo: dist.log_prob(actions).sum(dim=1) and
+// dist.entropy()) for one drone.  lp: actor_sample's own sequence on the given
+// bits (the factors multiplied in the order k = 0, 1, 2, one logf, the same
+// NaN propagation), so for the bits actor_sample drew from the same prob it is
+// the same float.  ent: the sum over the three factors of -(pc log pc + (1 -
+// pc) log(1 - pc)) on the probability clamped to [FLT_EPSILON, 1 -
+// FLT_EPSILON] (torch's clamp_probs; Bernoulli.entropy is the binary cross
+// entropy of the clamped logit against p itself, the same number for p in the
+// clamp's range).  The notebook's own clamp(1e-8, 1 - 1e-8) before it changes
+// nothing in float32: 1 - 1e-8 rounds to 1, above every Sigmoid output that is
+// not 1 already, and 1e-8 lies below FLT_EPSILON, so clamp_probs subsumes it.
+// NaN probabilities give a NaN entropy, as they give a NaN log-probability.
+__device__ __forceinline__ void actor_evaluate(const float (&prob)[3], uint32_t bits, float& lp, float& ent) {
+    float pr = 1.0f;
+    ent = 0.0f;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        pr *= bernoulli_factor(prob[k], (bits >> k) & 1u);
+        const float pc = bernoulli_factor(prob[k], true), qc = 1.0f - pc;
+        ent -= pc * logf(pc) + qc * logf(qc);
+    }
+    const float poison = prob[0] + prob[1] + prob[2];
+    lp = fmaf(poison, 0.0f, logf(pr));
+    ent = fmaf(poison, 0.0f, ent);
+}
+
 // Action selection of the notebooks' evaluate_policy* cells (the three
 // *_inference.ipynb, Policy_Gradients.ipynb "Eval", Actor_Critic_PPO.ipynb
 // evaluate_policy):

@@ -270,6 +270,15 @@ struct SampledArgs : FwdArgs {
     float* probs_used;
 };
 
+// dd_mlp_evaluate_actions' launch: FwdArgs (out = probs; no draw, so actions,
+// seed, step and env_id_base are unused) and the given actions, their format
+// as the type.
+template <int kFmt>
+struct EvalArgs : FwdArgs {
+    const void* given;
+    float* entropy;
+};
+
 // Layer 1's B operands for lane (c, h) of a tile: obs[d][8h + q] (kSplit) or
 // obs[d][2q + h], zero past column 14 and past the last row.
 template <bool kSplit>
@@ -349,6 +358,39 @@ __device__ __forceinline__ void emit_outputs(const SampledArgs<kMode>& p, int64_
 #pragma unroll
             for (int k = 0; k < 3; ++k) p.probs_used[d * 3 + k] = used[k];
         }
+    }
+}
+
+// Row d's given action as dd_step's bitmask: DD_ACT_BITMASK, bits 0-2 of the
+// byte; DD_ACT_F32X3, nonzero = on (lane_io.h load_action's rule).  64-bit row
+// index: a training batch is not cut into chunks.
+template <int kFmt>
+__device__ __forceinline__ uint32_t given_bits(const void* actions, int64_t d) {
+    if constexpr (kFmt == DD_ACT_BITMASK) {
+        return static_cast<const uint8_t*>(actions)[d] & 7u;
+    } else {
+        static_assert(kFmt == DD_ACT_F32X3, "given actions are bitmasks or float triples");
+        const float* a = static_cast<const float*>(actions) + d * 3;
+        return (a[0] != 0.0f ? 1u : 0u) | (a[1] != 0.0f ? 2u : 0u) | (a[2] != 0.0f ? 4u : 0u);
+    }
+}
+
+// The actor's outputs of one drone with its action given (mlp_core.h
+// actor_evaluate).
+template <int K, int kFmt>
+__device__ __forceinline__ void emit_outputs(const EvalArgs<kFmt>& p, int64_t d, const float (&z)[K]) {
+    static_assert(K == 3, "scoring actions is the actor's");
+    float prob[3];
+    actor_probs(z, prob);
+    if (p.out) {
+#pragma unroll
+        for (int k = 0; k < 3; ++k) p.out[d * 3 + k] = prob[k];
+    }
+    if (p.log_prob || p.entropy) {
+        float lp, ent;
+        actor_evaluate(prob, given_bits<kFmt>(p.given, d), lp, ent);
+        if (p.log_prob) p.log_prob[d] = lp;
+        if (p.entropy) p.entropy[d] = ent;
     }
 }
 
@@ -443,7 +485,8 @@ __device__ __forceinline__ void wait_layers23() {
 }
 
 // A: FwdArgs (dd_mlp_forward: the instructions it had before the action
-// selection existed) or SampledArgs<mode> (dd_mlp_forward_sampled, K = 3).
+// selection existed), SampledArgs<mode> (dd_mlp_forward_sampled, K = 3) or
+// EvalArgs<format> (dd_mlp_evaluate_actions, K = 3).
 template <int K, bool kSplit, typename A>
 __global__ __launch_bounds__(kThreads) void mlp_kernel(const float* __restrict__ packed, A p) {
     extern __shared__ f32x4 lds4[];
@@ -515,6 +558,15 @@ hipError_t launch_sampled(const float* packed, const FwdArgs& a, const DDSamplin
     }
 }
 
+template <bool kSplit, int kFmt>
+hipError_t launch_eval(const float* packed, const DDMlpEvalIO& io, hipStream_t s) {
+    EvalArgs<kFmt> p;
+    static_cast<FwdArgs&>(p) = FwdArgs{io.obs, io.probs, nullptr, io.log_prob, 0, 0, 0, io.n};
+    p.given = io.actions;
+    p.entropy = io.entropy;
+    return launch<3, kSplit>(packed, p, s);
+}
+
 }  // namespace mlp
 }  // namespace dd
 
@@ -567,6 +619,21 @@ int dd_mlp_forward_sampled(const float* packed, int32_t compute, int32_t out_dim
     if (compute == DD_MLP_F16X3)
         return out_dim == 3 ? dd::mlp::launch<3, true>(packed, a, s) : dd::mlp::launch<1, true>(packed, a, s);
     return out_dim == 3 ? dd::mlp::launch<3, false>(packed, a, s) : dd::mlp::launch<1, false>(packed, a, s);
+}
+
+int dd_mlp_evaluate_actions(const float* packed, int32_t compute, const DDMlpEvalIO* io, void* stream) {
+    if (!io || io->n < 0) return hipErrorInvalidValue;
+    if (io->action_format != DD_ACT_BITMASK && io->action_format != DD_ACT_F32X3) return hipErrorInvalidValue;
+    if (compute != DD_MLP_F32 && compute != DD_MLP_F16X3) return hipErrorInvalidValue;
+    if (io->n == 0) return hipSuccess;
+    if (!packed || !io->obs || !io->actions) return hipErrorInvalidValue;
+    if (reinterpret_cast<uintptr_t>(packed) & 15u) return hipErrorInvalidValue;  // 16-byte fragments / LDS-DMA
+    const hipStream_t s = (hipStream_t)stream;
+    if (io->action_format == DD_ACT_BITMASK)
+        return compute == DD_MLP_F16X3 ? dd::mlp::launch_eval<true, DD_ACT_BITMASK>(packed, *io, s)
+                                       : dd::mlp::launch_eval<false, DD_ACT_BITMASK>(packed, *io, s);
+    return compute == DD_MLP_F16X3 ? dd::mlp::launch_eval<true, DD_ACT_F32X3>(packed, *io, s)
+                                   : dd::mlp::launch_eval<false, DD_ACT_F32X3>(packed, *io, s);
 }
 
 }  // extern "C"

@@ -13,7 +13,9 @@ built from rollout buffers on device (:func:`ppo_batch`,
 :func:`reinforce_batch`, :func:`collect_ppo`), from each lane's first
 episode or from every episode of an auto-reset rollout
 (:func:`ppo_episodes_batch`, :func:`reinforce_episodes_batch`,
-:func:`collect_ppo_steps`).
+:func:`collect_ppo_steps`); and the PPO notebook's losses, ratio statistics and
+head gradients on such a batch (:func:`ppo_losses`,
+:meth:`MlpNet.evaluate_actions`, :meth:`MlpNet.load_state_dict`).
 """
 from .config import EnvConfig
 from .vec_env import OBS_KEYS, StepInfo, VecDroneEnv
@@ -23,6 +25,7 @@ from .gae import gae
 from .policy import MlpNet
 from .train_batch import collect_ppo, ppo_batch, reinforce_batch
 from .train_batch import collect_ppo_steps, ppo_episodes_batch, reinforce_episodes_batch
+from .ppo_loss import PpoLosses, ppo_losses
 
 __all__ = [
     "EnvConfig", "VecDroneEnv", "StepInfo", "OBS_KEYS",
@@ -30,5 +33,6 @@ __all__ = [
     "shard_bounds", "dist_env", "gather_obs", "gae", "MlpNet",
     "ppo_batch", "reinforce_batch", "collect_ppo",
     "ppo_episodes_batch", "reinforce_episodes_batch", "collect_ppo_steps",
+    "ppo_losses", "PpoLosses",
 ]
 __version__ = "0.1.0"

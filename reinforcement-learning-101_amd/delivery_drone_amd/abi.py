@@ -21,7 +21,9 @@ __all__ = [
     "DD_SAMPLE_BERNOULLI", "DD_SAMPLE_TEMPERED", "DD_SAMPLE_GREEDY",
     "DDConfig", "DDState", "DDStepIO", "DDRolloutIO", "DDMlpParams", "DDMlpIO", "DDPolicyRolloutIO", "DDSampling",
     "DDEpisodeStats", "DD_BATCH_GAE", "DD_BATCH_RETURNS", "DDBatchLayout", "DDBatchGatherIO", "DDBatchAdvIO",
-    "DD_EPISODES_DROP_OPEN", "DDEpisodeLayout",
+    "DD_EPISODES_DROP_OPEN", "DDEpisodeLayout", "DDMlpEvalIO", "DDPpoLossIO",
+    "DD_PPO_TOTAL_LOSS", "DD_PPO_POLICY_LOSS", "DD_PPO_VALUE_LOSS", "DD_PPO_ENTROPY", "DD_PPO_RATIO_MEAN",
+    "DD_PPO_RATIO_MIN", "DD_PPO_RATIO_MAX", "DD_PPO_RATIO_STD", "DD_PPO_CLIPPED_FRAC", "DD_PPO_RESULTS",
     "sampling_mode", "lib", "load", "library_path", "check",
     "NativeLibraryError",
 ]
@@ -41,6 +43,8 @@ DD_MEM_DEFAULT, DD_MEM_CONTIGUOUS = 0, 1
 DD_SAMPLE_BERNOULLI, DD_SAMPLE_TEMPERED, DD_SAMPLE_GREEDY = 0, 1, 2
 DD_BATCH_GAE, DD_BATCH_RETURNS = 0, 1
 DD_EPISODES_DROP_OPEN = 1
+(DD_PPO_TOTAL_LOSS, DD_PPO_POLICY_LOSS, DD_PPO_VALUE_LOSS, DD_PPO_ENTROPY, DD_PPO_RATIO_MEAN, DD_PPO_RATIO_MIN,
+ DD_PPO_RATIO_MAX, DD_PPO_RATIO_STD, DD_PPO_CLIPPED_FRAC, DD_PPO_RESULTS) = range(10)
 
 _D = ctypes.c_double
 _I = ctypes.c_int32
@@ -163,6 +167,20 @@ class DDEpisodeLayout(ctypes.Structure):
                 ("ep_offset", ctypes.c_void_p)]
 
 
+class DDMlpEvalIO(ctypes.Structure):
+    _fields_ = [("obs", ctypes.c_void_p), ("actions", ctypes.c_void_p), ("action_format", _I), ("_pad", _I),
+                ("probs", ctypes.c_void_p), ("log_prob", ctypes.c_void_p), ("entropy", ctypes.c_void_p),
+                ("n", ctypes.c_int64)]
+
+
+class DDPpoLossIO(ctypes.Structure):
+    _fields_ = [("log_prob", ctypes.c_void_p), ("entropy", ctypes.c_void_p), ("probs", ctypes.c_void_p),
+                ("values", ctypes.c_void_p), ("old_log_prob", ctypes.c_void_p), ("advantages", ctypes.c_void_p),
+                ("returns", ctypes.c_void_p), ("actions", ctypes.c_void_p), ("action_format", _I), ("_pad", _I),
+                ("clip_epsilon", _D), ("entropy_coef", _D), ("value_coef", _D), ("result", ctypes.c_void_p),
+                ("ratio", ctypes.c_void_p), ("grad_logits", ctypes.c_void_p), ("grad_values", ctypes.c_void_p)]
+
+
 def sampling_mode(temperature) -> int:
     """The ``DD_SAMPLE_*`` mode of a notebook ``temperature``: 1 is the plain
     Bernoulli draw, 0 greedy (``probs > 0.5``), any other positive finite value
@@ -244,6 +262,10 @@ EXPORTS = {
                                           ctypes.c_void_p]),
     "dd_episodes_advantages": (ctypes.c_int, [ctypes.POINTER(DDEpisodeLayout), ctypes.POINTER(DDBatchAdvIO),
                                               ctypes.c_int64, ctypes.c_int64, ctypes.c_void_p]),
+    "dd_mlp_evaluate_actions": (ctypes.c_int, [ctypes.c_void_p, _I, ctypes.POINTER(DDMlpEvalIO), ctypes.c_void_p]),
+    "dd_ppo_loss_workspace": (ctypes.c_int64, []),
+    "dd_ppo_losses": (ctypes.c_int, [ctypes.POINTER(DDPpoLossIO), ctypes.c_int64, ctypes.c_void_p,
+                                     ctypes.c_void_p]),
 }
 
 #: symbols a timing-only lab build (tools/build_variants.sh) or an older
@@ -252,7 +274,8 @@ _LAB_OPTIONAL = ("dd_build_info", "dd_selftest_sqrt", "dd_rollout_kernel", "dd_d
                  "dd_wall_clock_khz", "dd_device_alloc", "dd_device_free", "dd_mlp_forward_sampled",
                  "dd_policy_rollout_sampled", "dd_batch_workspace", "dd_batch_plan", "dd_batch_gather",
                  "dd_batch_advantages", "dd_batch_normalize", "dd_episodes_workspace", "dd_episodes_count",
-                 "dd_episodes_fill", "dd_episodes_gather", "dd_episodes_advantages")
+                 "dd_episodes_fill", "dd_episodes_gather", "dd_episodes_advantages", "dd_mlp_evaluate_actions",
+                 "dd_ppo_loss_workspace", "dd_ppo_losses")
 
 
 class NativeLibraryError(RuntimeError):

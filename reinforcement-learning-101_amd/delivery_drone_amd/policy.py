@@ -60,6 +60,15 @@ class MlpNet:
         self.compute = compute
         self._mode = _COMPUTE[compute]
         self._lib = library if library is not None else abi.lib()
+        self.ln_eps = float(ln_eps)
+        self._src, self.out_dim = self._validated(state_dict)
+        self.packed = torch.empty(int(self._lib.dd_mlp_packed_floats()), dtype=torch.float32, device=self.device)
+        self._pack()
+
+    def _validated(self, state_dict: Mapping[str, torch.Tensor]):
+        """The constructor's checks of a state_dict (keys, shapes, the f16x3
+        operand ranges): its float32 device tensors and K, or an exception."""
+        compute = self.compute
         sd = {k[len("network."):] if k.startswith("network.") else k: v for k, v in state_dict.items()}
         missing = [k for k in STATE_DICT_KEYS if k not in sd]
         if missing:
@@ -70,18 +79,15 @@ class MlpNet:
         k_out = sd["9.weight"].shape[0]
         if k_out not in (1, 3) or tuple(sd["9.weight"].shape) != (k_out, 64) or tuple(sd["9.bias"].shape) != (k_out,):
             raise ValueError("last layer must be Linear(64, 3) (actor) or Linear(64, 1) (critic)")
-        self.out_dim = int(k_out)
-        self.ln_eps = float(ln_eps)
-        # keep the source tensors alive until the pack kernel has read them
-        self._src = {k: torch.as_tensor(sd[k]).detach().to(device=self.device, dtype=torch.float32).contiguous()
-                     for k in STATE_DICT_KEYS}
+        src = {k: torch.as_tensor(sd[k]).detach().to(device=self.device, dtype=torch.float32).contiguous()
+               for k in STATE_DICT_KEYS}
         if compute == "f16x3":
             # the hidden Linears' weights go into f16 halves x16 (kWScale) after
             # centring over their outputs (|w - mean| <= 2 max|w|): beyond the f16
             # range the hi half is inf and every probability NaN, so refuse such
             # weights here (observations must stay below 1023 as well)
             for k in ("0.weight", "3.weight", "6.weight"):
-                w = self._src[k]
+                w = src[k]
                 if not bool(torch.isfinite(w).all()) or float(w.abs().max()) >= 65504.0 / 32:
                     raise ValueError(f"{k}: compute='f16x3' needs finite weights below 2047 in magnitude "
                                      "(the f16 range after centring and x16); use compute='f32'")
@@ -89,14 +95,33 @@ class MlpNet:
             # split_pair_relu), which needs it below 2048: |gamma| sqrt(rows) +
             # |beta| bounds a LayerNorm's output
             for g, b, rows in (("1.weight", "1.bias", 128), ("4.weight", "4.bias", 128), ("7.weight", "7.bias", 64)):
-                bound = float(self._src[g].abs().max()) * rows ** 0.5 * (1 + 2 ** -8) + float(self._src[b].abs().max())
+                bound = float(src[g].abs().max()) * rows ** 0.5 * (1 + 2 ** -8) + float(src[b].abs().max())
                 if not bound < 128.0:
                     raise ValueError(f"{g}/{b}: compute='f16x3' needs LayerNorm outputs below 128 "
                                      f"(max|weight| sqrt({rows}) + max|bias| = {bound:.4g}); use compute='f32'")
+        return src, int(k_out)
+
+    def _pack(self):
+        """dd_mlp_pack of ``_src`` into ``packed`` on the current stream."""
         p = abi.DDMlpParams(*[self._src[k].data_ptr() for k in STATE_DICT_KEYS], self.out_dim, self.ln_eps)
-        self.packed = torch.empty(int(self._lib.dd_mlp_packed_floats()), dtype=torch.float32, device=self.device)
         abi.check(self._lib.dd_mlp_pack(ctypes.byref(p), self._mode, self.packed.data_ptr(), self._stream()),
                   "dd_mlp_pack")
+
+    def load_state_dict(self, state_dict: Mapping[str, torch.Tensor]) -> "MlpNet":
+        """New weights into the same ``packed`` buffer, on the current stream.
+
+        The state_dict is checked exactly as the constructor checks one (keys,
+        shapes, the ``f16x3`` operand ranges); a refused one raises and leaves
+        the old parameters in place.  ``packed`` keeps its address, so a
+        captured graph or a ``policy_rollout`` that holds the pointer sees the
+        new weights at its next launch after this one on the stream.  The last
+        layer may change between ``Linear(64, 3)`` and ``Linear(64, 1)`` (the
+        buffer's size is the same); ``out_dim`` follows, and a launch that
+        still asks for the other K gets NaN by the layout tag."""
+        src, out_dim = self._validated(state_dict)
+        self._src, self.out_dim = src, out_dim  # kept alive until the pack kernel has read them, as the constructor's
+        self._pack()
+        return self
 
     @classmethod
     def from_file(cls, path: str, **kw) -> "MlpNet":
@@ -178,3 +203,41 @@ class MlpNet:
         self._run(obs, out=p, actions=actions, log_prob=log_prob, seed=seed, step=step, env_id_base=env_id_base,
                   sampling=sampling)
         return (actions, log_prob, p) if probs else (actions, log_prob)
+
+    def evaluate_actions(self, obs: torch.Tensor, actions: torch.Tensor, *, probs: bool = False,
+                         log_prob_out: Optional[torch.Tensor] = None, entropy_out: Optional[torch.Tensor] = None):
+        """Score given actions as ``compute_ppo_losses`` does (actor only):
+        ``dist = Bernoulli(probs=policy(obs))``, ``dist.log_prob(actions).sum(1)``
+        and ``dist.entropy().sum(1)`` (``dd_mlp_evaluate_actions``).
+
+        ``actions`` is the uint8 ``[N]`` bitmask :meth:`act` returns, or the
+        float32 ``[N, 3]`` tensor of a training batch (nonzero = on).  Returns
+        ``(log_prob, entropy)`` or ``(log_prob, entropy, probs)``, float32
+        ``[N]`` and ``[N, 3]``.  For the actions :meth:`act` drew on the same
+        rows, ``log_prob`` has the bits of :meth:`act`'s own."""
+        if self.out_dim != 3:
+            raise ValueError("evaluate_actions() needs the actor (out_dim 3)")
+        obs = self._obs(obs)
+        n = obs.shape[0]
+        if not isinstance(actions, torch.Tensor) or actions.device != self.device:
+            raise ValueError(f"actions must be a tensor on {self.device}")
+        if actions.dtype == torch.uint8 and tuple(actions.shape) == (n,):
+            fmt = abi.DD_ACT_BITMASK
+        elif actions.dtype == torch.float32 and tuple(actions.shape) == (n, 3):
+            fmt = abi.DD_ACT_F32X3
+        else:
+            raise ValueError(f"actions must be uint8 ({n},) bitmasks or float32 ({n}, 3), got {actions.dtype} "
+                             f"{tuple(actions.shape)}")
+        actions = actions.contiguous()
+        for name, t in (("log_prob_out", log_prob_out), ("entropy_out", entropy_out)):
+            if t is not None and (tuple(t.shape) != (n,) or t.dtype != torch.float32 or not t.is_contiguous()
+                                  or t.device != self.device):
+                raise ValueError(f"{name} must be a contiguous float32 tensor of shape ({n},) on {self.device}")
+        lp = log_prob_out if log_prob_out is not None else torch.empty(n, dtype=torch.float32, device=self.device)
+        ent = entropy_out if entropy_out is not None else torch.empty(n, dtype=torch.float32, device=self.device)
+        p = torch.empty(n, 3, dtype=torch.float32, device=self.device) if probs else None
+        io = abi.DDMlpEvalIO(obs.data_ptr(), actions.data_ptr(), fmt, 0, p.data_ptr() if probs else None,
+                             lp.data_ptr(), ent.data_ptr(), n)
+        abi.check(self._lib.dd_mlp_evaluate_actions(self.packed.data_ptr(), self._mode, ctypes.byref(io),
+                                                    self._stream()), "dd_mlp_evaluate_actions")
+        return (lp, ent, p) if probs else (lp, ent)
