@@ -819,6 +819,49 @@ typedef struct DDPpoLossIO {
 int64_t dd_ppo_loss_workspace(void);
 int dd_ppo_losses(const DDPpoLossIO *io, int64_t m, void *workspace, void *stream);
 
+/* ---- The networks' backward pass (additions to ABI 13) ----------------------
+ * The parameter gradients of DroneGamerBoi / DroneTeacherBoi from the gradient
+ * at the last Linear's output: for the actor the pre-Sigmoid logits, for the
+ * critic the value, i.e. dd_ppo_losses' grad_logits / grad_values.  What
+ * loss.backward() leaves in every parameter's .grad, then the notebook's
+ * clip_grad_norm_ (per network, with max_grad_norm).  Per layer (a = its input):
+ *   dy = da' [y > 0]          dgamma = sum_rows dy xh     dbeta = sum_rows dy
+ *   g = dy gamma              dh = rstd (g - mean(g) - xh mean(g xh))
+ *   dW = sum_rows dh (x) a    db = sum_rows dh            da = W^T dh
+ * (csrc/mlp_backward.hip's header).  Float32 on the f32 MFMA from the plain
+ * float32 parameters, whatever compute the forward was packed for; the
+ * forward is recomputed tile by tile, so the workspace does not grow with m.
+ * A fixed number of blocks each writes one partial gradient set; each element
+ * is then the partials' sum in a fixed order in double, rounded once, and the
+ * norm a fixed tree in double: the same bits on every run and every device.
+ * grads: the fourteen tensors in DDMlpParams' order and torch's shapes
+ * (w0 [128][15], ... w9 [K][64], b9 [K]).  grad_norm (nullable): the L2 norm
+ * over all fourteen, before clipping.  max_norm finite and > 0: every gradient
+ * is scaled by min(1, max_norm / (norm + 1e-6)); <= 0, +inf or NaN: no clipping.
+ * workspace: dd_mlp_backward_workspace() bytes, 16-byte aligned.
+ * hipErrorInvalidValue, before any HIP call: a null params, io, parameter or
+ * gradient pointer, m < 0, out_dim not 1 or 3, and with m > 0 a null states,
+ * grad_out or workspace (or a misaligned one).  m == 0 writes zeros and a zero
+ * norm.  All row indices are 64-bit. */
+typedef struct DDMlpGrads {
+    float *w0, *b0, *ln1_w, *ln1_b;
+    float *w3, *b3, *ln4_w, *ln4_b;
+    float *w6, *b6, *ln7_w, *ln7_b;
+    float *w9, *b9;
+} DDMlpGrads;
+
+typedef struct DDMlpBackwardIO {
+    const float *states;   /* [m][15]                                    */
+    const float *grad_out; /* [m][K]                                     */
+    DDMlpGrads grads;
+    double *grad_norm;     /* nullable                                   */
+    double max_norm;
+} DDMlpBackwardIO;
+
+int64_t dd_mlp_backward_workspace(void);
+int dd_mlp_backward(const DDMlpParams *params, const DDMlpBackwardIO *io, int64_t m, void *workspace,
+                    void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -15,7 +15,9 @@ episode or from every episode of an auto-reset rollout
 (:func:`ppo_episodes_batch`, :func:`reinforce_episodes_batch`,
 :func:`collect_ppo_steps`); and the PPO notebook's losses, ratio statistics and
 head gradients on such a batch (:func:`ppo_losses`,
-:meth:`MlpNet.evaluate_actions`, :meth:`MlpNet.load_state_dict`).
+:meth:`MlpNet.evaluate_actions`, :meth:`MlpNet.load_state_dict`) and the two
+networks' parameter gradients from them (:func:`ppo_grads`,
+:meth:`MlpNet.backward`).
 """
 from .config import EnvConfig
 from .vec_env import OBS_KEYS, StepInfo, VecDroneEnv
@@ -26,6 +28,7 @@ from .policy import MlpNet
 from .train_batch import collect_ppo, ppo_batch, reinforce_batch
 from .train_batch import collect_ppo_steps, ppo_episodes_batch, reinforce_episodes_batch
 from .ppo_loss import PpoLosses, ppo_losses
+from .ppo_grad import PpoGrads, ppo_grads
 
 __all__ = [
     "EnvConfig", "VecDroneEnv", "StepInfo", "OBS_KEYS",
@@ -33,6 +36,6 @@ __all__ = [
     "shard_bounds", "dist_env", "gather_obs", "gae", "MlpNet",
     "ppo_batch", "reinforce_batch", "collect_ppo",
     "ppo_episodes_batch", "reinforce_episodes_batch", "collect_ppo_steps",
-    "ppo_losses", "PpoLosses",
+    "ppo_losses", "PpoLosses", "ppo_grads", "PpoGrads",
 ]
 __version__ = "0.1.0"

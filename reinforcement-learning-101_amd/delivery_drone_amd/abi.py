@@ -21,7 +21,7 @@ __all__ = [
     "DD_SAMPLE_BERNOULLI", "DD_SAMPLE_TEMPERED", "DD_SAMPLE_GREEDY",
     "DDConfig", "DDState", "DDStepIO", "DDRolloutIO", "DDMlpParams", "DDMlpIO", "DDPolicyRolloutIO", "DDSampling",
     "DDEpisodeStats", "DD_BATCH_GAE", "DD_BATCH_RETURNS", "DDBatchLayout", "DDBatchGatherIO", "DDBatchAdvIO",
-    "DD_EPISODES_DROP_OPEN", "DDEpisodeLayout", "DDMlpEvalIO", "DDPpoLossIO",
+    "DD_EPISODES_DROP_OPEN", "DDEpisodeLayout", "DDMlpEvalIO", "DDPpoLossIO", "DDMlpGrads", "DDMlpBackwardIO",
     "DD_PPO_TOTAL_LOSS", "DD_PPO_POLICY_LOSS", "DD_PPO_VALUE_LOSS", "DD_PPO_ENTROPY", "DD_PPO_RATIO_MEAN",
     "DD_PPO_RATIO_MIN", "DD_PPO_RATIO_MAX", "DD_PPO_RATIO_STD", "DD_PPO_CLIPPED_FRAC", "DD_PPO_RESULTS",
     "sampling_mode", "lib", "load", "library_path", "check",
@@ -181,6 +181,19 @@ class DDPpoLossIO(ctypes.Structure):
                 ("ratio", ctypes.c_void_p), ("grad_logits", ctypes.c_void_p), ("grad_values", ctypes.c_void_p)]
 
 
+class DDMlpGrads(ctypes.Structure):
+    """The fourteen gradients, in ``DDMlpParams``' order."""
+
+    _fields_ = [(name, ctypes.c_void_p) for name in (
+        "w0", "b0", "ln1_w", "ln1_b", "w3", "b3", "ln4_w", "ln4_b",
+        "w6", "b6", "ln7_w", "ln7_b", "w9", "b9")]
+
+
+class DDMlpBackwardIO(ctypes.Structure):
+    _fields_ = [("states", ctypes.c_void_p), ("grad_out", ctypes.c_void_p), ("grads", DDMlpGrads),
+                ("grad_norm", ctypes.c_void_p), ("max_norm", _D)]
+
+
 def sampling_mode(temperature) -> int:
     """The ``DD_SAMPLE_*`` mode of a notebook ``temperature``: 1 is the plain
     Bernoulli draw, 0 greedy (``probs > 0.5``), any other positive finite value
@@ -266,6 +279,9 @@ EXPORTS = {
     "dd_ppo_loss_workspace": (ctypes.c_int64, []),
     "dd_ppo_losses": (ctypes.c_int, [ctypes.POINTER(DDPpoLossIO), ctypes.c_int64, ctypes.c_void_p,
                                      ctypes.c_void_p]),
+    "dd_mlp_backward_workspace": (ctypes.c_int64, []),
+    "dd_mlp_backward": (ctypes.c_int, [ctypes.POINTER(DDMlpParams), ctypes.POINTER(DDMlpBackwardIO), ctypes.c_int64,
+                                       ctypes.c_void_p, ctypes.c_void_p]),
 }
 
 #: symbols a timing-only lab build (tools/build_variants.sh) or an older
@@ -275,7 +291,7 @@ _LAB_OPTIONAL = ("dd_build_info", "dd_selftest_sqrt", "dd_rollout_kernel", "dd_d
                  "dd_policy_rollout_sampled", "dd_batch_workspace", "dd_batch_plan", "dd_batch_gather",
                  "dd_batch_advantages", "dd_batch_normalize", "dd_episodes_workspace", "dd_episodes_count",
                  "dd_episodes_fill", "dd_episodes_gather", "dd_episodes_advantages", "dd_mlp_evaluate_actions",
-                 "dd_ppo_loss_workspace", "dd_ppo_losses")
+                 "dd_ppo_loss_workspace", "dd_ppo_losses", "dd_mlp_backward_workspace", "dd_mlp_backward")
 
 
 class NativeLibraryError(RuntimeError):

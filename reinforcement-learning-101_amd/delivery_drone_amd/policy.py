@@ -17,12 +17,16 @@ include/dronestep.h ``DD_MLP_F16X3``).
 The actor also does the collection loop's ``Bernoulli(probs).sample()`` and
 ``.log_prob(actions).sum(dim=1)`` (:857-859) in the same launch, returning the
 actions as the ``dd_step`` bitmask, so a policy-driven rollout never leaves
-the device.
+the device.  :meth:`MlpNet.backward` is the training side: the parameter
+gradients from the gradient at the network's output (``dd_mlp_backward``,
+float32 MFMA with the forward recomputed tile by tile) and the notebook's
+``clip_grad_norm_``.
 """
 from __future__ import annotations
 
 import ctypes
-from typing import Mapping, Optional
+import math
+from typing import Dict, Mapping, Optional, Tuple
 
 import torch
 
@@ -241,3 +245,67 @@ class MlpNet:
         abi.check(self._lib.dd_mlp_evaluate_actions(self.packed.data_ptr(), self._mode, ctypes.byref(io),
                                                     self._stream()), "dd_mlp_evaluate_actions")
         return (lp, ent, p) if probs else (lp, ent)
+
+    def grad_numel(self) -> int:
+        """Elements of the flat gradient vector :meth:`backward` fills (the
+        fourteen tensors of ``STATE_DICT_KEYS``, concatenated)."""
+        return sum(math.prod(_SHAPES[k]) for k in _SHAPES) + 65 * self.out_dim
+
+    def backward(self, states: torch.Tensor, grad_out: torch.Tensor, *, max_norm: Optional[float] = None,
+                 out: Optional[torch.Tensor] = None) -> Tuple[Dict[str, torch.Tensor], torch.Tensor]:
+        """The parameter gradients autograd leaves when it starts from
+        ``grad_out`` at the last Linear's output on ``states``
+        (``dd_mlp_backward``): for the actor ``grad_out [M, 3]`` is the
+        gradient at the pre-Sigmoid logits, for the critic ``[M]`` (or ``[M,
+        1]``) the gradient at the value, i.e. ``ppo_losses(...,
+        grads=True)``'s ``grad_logits`` / ``grad_values``.
+
+        Returns ``(grads, grad_norm)``.  ``grads`` maps ``STATE_DICT_KEYS`` to
+        float32 tensors in ``nn.Linear`` / ``nn.LayerNorm`` shapes, views into
+        one flat buffer in that order (``out``, a contiguous float32 tensor of
+        :meth:`grad_numel` elements, or a new one), so ``grads["0.weight"]``'s
+        storage is also the flat gradient vector.  ``grad_norm`` is the L2
+        norm over all fourteen before clipping, a 0-d float64 device tensor.
+        ``max_norm`` (finite, positive) applies the notebook's
+        ``clip_grad_norm_(parameters, max_norm)``: every gradient times
+        ``min(1, max_norm / (norm + 1e-6))``.  Float32 arithmetic from the
+        float32 parameters whatever ``compute`` is; the same bits on every run
+        and every device.  ``M == 0`` gives zeros.  Runs on the current stream
+        and reads nothing back."""
+        states = self._obs(states)
+        m = states.shape[0]
+        want = (m, 3) if self.out_dim == 3 else (m,)
+        if not isinstance(grad_out, torch.Tensor) or grad_out.device != self.device:
+            raise ValueError(f"grad_out must be a tensor on {self.device}")
+        if self.out_dim == 1 and tuple(grad_out.shape) == (m, 1):
+            grad_out = grad_out.reshape(m)
+        if tuple(grad_out.shape) != want:
+            raise ValueError(f"grad_out must be {want} for out_dim {self.out_dim}, got {tuple(grad_out.shape)}")
+        grad_out = grad_out.detach().to(torch.float32).contiguous()
+        if max_norm is not None and math.isnan(float(max_norm)):
+            raise ValueError("max_norm must not be NaN")
+        total = self.grad_numel()
+        if out is None:
+            out = torch.empty(total, dtype=torch.float32, device=self.device)
+        elif (not isinstance(out, torch.Tensor) or tuple(out.shape) != (total,) or out.dtype != torch.float32
+              or not out.is_contiguous() or out.device != self.device):
+            raise ValueError(f"out must be a contiguous float32 tensor of shape ({total},) on {self.device}")
+        shapes = dict(_SHAPES)
+        shapes["9.weight"], shapes["9.bias"] = (self.out_dim, 64), (self.out_dim,)
+        grads, first = {}, 0
+        for k in STATE_DICT_KEYS:
+            n = math.prod(shapes[k])
+            grads[k] = out[first:first + n].view(shapes[k])
+            first += n
+        norm = torch.empty((), dtype=torch.float64, device=self.device)
+        ws = getattr(self, "_backward_ws", None)
+        if ws is None:  # the packed weight images and the blocks' partial sums: a fixed size, kept
+            ws = self._backward_ws = torch.empty(int(self._lib.dd_mlp_backward_workspace()) // 8, dtype=torch.int64,
+                                                 device=self.device)
+        p = abi.DDMlpParams(*[self._src[k].data_ptr() for k in STATE_DICT_KEYS], self.out_dim, self.ln_eps)
+        io = abi.DDMlpBackwardIO(states.data_ptr(), grad_out.data_ptr(),
+                                 abi.DDMlpGrads(*[grads[k].data_ptr() for k in STATE_DICT_KEYS]), norm.data_ptr(),
+                                 float(max_norm) if max_norm is not None else 0.0)
+        abi.check(self._lib.dd_mlp_backward(ctypes.byref(p), ctypes.byref(io), m, ws.data_ptr(), self._stream()),
+                  "dd_mlp_backward")
+        return grads, norm
