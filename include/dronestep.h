@@ -862,6 +862,75 @@ int64_t dd_mlp_backward_workspace(void);
 int dd_mlp_backward(const DDMlpParams *params, const DDMlpBackwardIO *io, int64_t m, void *workspace,
                     void *stream);
 
+/* ---- AdamW on one network's parameters (additions to ABI 13) ----------------
+ * One step of torch.optim.AdamW (decoupled weight decay, amsgrad=False,
+ * maximize=False), the training cell's policy_optimizer.step() /
+ * critic_optimizer.step():
+ *   p' = p (1 - lr wd);  m' = beta1 m + (1 - beta1) g;  v' = beta2 v + (1 - beta2) g g
+ *   p'' = p' - (lr / (1 - beta1^t)) (m' / (sqrt(v') / sqrt(1 - beta2^t) + eps))
+ * params, grads, exp_avg, exp_avg_sq: flat float32 buffers of 27,456 + 65 K
+ * elements, the fourteen tensors in DDMlpParams' order and torch's shapes (the
+ * layout of dd_mlp_backward's gradients when they share one buffer).  Every
+ * element is evaluated in double from the four float32 inputs, in exactly the
+ * order written above (1 - lr wd, 1 - beta1, 1 - beta2 are formed once on the
+ * host; no contraction), and p'', m', v' are each rounded to float32 once;
+ * float32 denormals are kept.  The step count lives on the device:
+ * DDAdamWState holds step, the running products beta1^t and beta2^t (one
+ * multiplication per step, not pow) and a status word; the kernel advances
+ * them, the host never passes t, so a captured launch can be replayed.
+ *
+ * compute == DD_MLP_F16X3: the candidate parameters must be ones the f16x3
+ * forward can hold: every element of w0, w3, w6 finite and below 65504 / 32 in
+ * magnitude, and for each LayerNorm max|gamma| sqrt(rows) (1 + 2^-8) +
+ * max|beta| < 128 (in double; a NaN fails).  If they are not, nothing is
+ * committed (params, exp_avg, exp_avg_sq, step and the products keep their
+ * bits, packed is rebuilt from the unchanged parameters) and
+ * DD_ADAMW_REFUSED is or-ed into status, where it stays.  DD_MLP_F32: no check.
+ * One launch of one 1,024-thread block: the candidates stay in registers
+ * across the verdict's block maximum.  No atomics; the same bits on every run.
+ * packed (nullable): dd_mlp_pack of the updated parameters into it afterwards,
+ * on the same stream (ln_eps as DDMlpParams').
+ *
+ * dd_adamw_init zeroes exp_avg, exp_avg_sq (nullable together, count
+ * elements), step and status and sets the products to 1, on the stream.
+ * hipErrorInvalidValue, before any launch: a null io, hyper, state or buffer,
+ * out_dim not 1 or 3, an unknown compute, a hyper-parameter that is not
+ * finite or is negative, a beta outside [0, 1), a packed that is not 16-byte
+ * aligned or comes with ln_eps <= 0, a negative count. */
+typedef struct DDAdamWHyper {
+    double lr;
+    double beta1;
+    double beta2;
+    double eps;
+    double weight_decay;
+} DDAdamWHyper;
+
+#define DD_ADAMW_REFUSED 1
+typedef struct DDAdamWState {
+    int64_t step;     /* t: steps committed                         */
+    double beta1_t;   /* beta1^t, 1 at t = 0                        */
+    double beta2_t;   /* beta2^t                                    */
+    int32_t status;   /* DD_ADAMW_* bits, sticky                    */
+    int32_t _pad;
+} DDAdamWState;
+
+typedef struct DDAdamWIO {
+    float *params;         /* [27456 + 65 K]                            */
+    const float *grads;    /* same length                               */
+    float *exp_avg;        /* same length                               */
+    float *exp_avg_sq;     /* same length                               */
+    DDAdamWState *state;   /* device, dd_adamw_state_bytes(), 8-aligned */
+    float *packed;         /* nullable: the network's dd_mlp_pack image */
+    int32_t out_dim;       /* K: 3 actor, 1 critic                      */
+    int32_t compute;       /* DD_MLP_F32 or DD_MLP_F16X3                */
+    float ln_eps;          /* for the repack                            */
+    int32_t _pad;
+} DDAdamWIO;
+
+int64_t dd_adamw_state_bytes(void);
+int dd_adamw_init(float *exp_avg, float *exp_avg_sq, int64_t count, DDAdamWState *state, void *stream);
+int dd_adamw_step(const DDAdamWHyper *hyper, const DDAdamWIO *io, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

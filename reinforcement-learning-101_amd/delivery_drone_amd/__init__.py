@@ -17,7 +17,9 @@ episode or from every episode of an auto-reset rollout
 head gradients on such a batch (:func:`ppo_losses`,
 :meth:`MlpNet.evaluate_actions`, :meth:`MlpNet.load_state_dict`) and the two
 networks' parameter gradients from them (:func:`ppo_grads`,
-:meth:`MlpNet.backward`).
+:meth:`MlpNet.backward`); and the notebook's two AdamW steps and its whole
+epoch loop on device (:class:`AdamW`, :func:`ppo_update`,
+:meth:`MlpNet.flat_parameters`).
 """
 from .config import EnvConfig
 from .vec_env import OBS_KEYS, StepInfo, VecDroneEnv
@@ -29,6 +31,7 @@ from .train_batch import collect_ppo, ppo_batch, reinforce_batch
 from .train_batch import collect_ppo_steps, ppo_episodes_batch, reinforce_episodes_batch
 from .ppo_loss import PpoLosses, ppo_losses
 from .ppo_grad import PpoGrads, ppo_grads
+from .adamw import AdamW, PpoUpdate, ppo_update
 
 __all__ = [
     "EnvConfig", "VecDroneEnv", "StepInfo", "OBS_KEYS",
@@ -37,5 +40,6 @@ __all__ = [
     "ppo_batch", "reinforce_batch", "collect_ppo",
     "ppo_episodes_batch", "reinforce_episodes_batch", "collect_ppo_steps",
     "ppo_losses", "PpoLosses", "ppo_grads", "PpoGrads",
+    "AdamW", "ppo_update", "PpoUpdate",
 ]
 __version__ = "0.1.0"

@@ -24,6 +24,7 @@ __all__ = [
     "DD_EPISODES_DROP_OPEN", "DDEpisodeLayout", "DDMlpEvalIO", "DDPpoLossIO", "DDMlpGrads", "DDMlpBackwardIO",
     "DD_PPO_TOTAL_LOSS", "DD_PPO_POLICY_LOSS", "DD_PPO_VALUE_LOSS", "DD_PPO_ENTROPY", "DD_PPO_RATIO_MEAN",
     "DD_PPO_RATIO_MIN", "DD_PPO_RATIO_MAX", "DD_PPO_RATIO_STD", "DD_PPO_CLIPPED_FRAC", "DD_PPO_RESULTS",
+    "DD_ADAMW_REFUSED", "DDAdamWHyper", "DDAdamWState", "DDAdamWIO",
     "sampling_mode", "lib", "load", "library_path", "check",
     "NativeLibraryError",
 ]
@@ -45,6 +46,8 @@ DD_BATCH_GAE, DD_BATCH_RETURNS = 0, 1
 DD_EPISODES_DROP_OPEN = 1
 (DD_PPO_TOTAL_LOSS, DD_PPO_POLICY_LOSS, DD_PPO_VALUE_LOSS, DD_PPO_ENTROPY, DD_PPO_RATIO_MEAN, DD_PPO_RATIO_MIN,
  DD_PPO_RATIO_MAX, DD_PPO_RATIO_STD, DD_PPO_CLIPPED_FRAC, DD_PPO_RESULTS) = range(10)
+
+DD_ADAMW_REFUSED = 1
 
 _D = ctypes.c_double
 _I = ctypes.c_int32
@@ -194,6 +197,22 @@ class DDMlpBackwardIO(ctypes.Structure):
                 ("grad_norm", ctypes.c_void_p), ("max_norm", _D)]
 
 
+class DDAdamWHyper(ctypes.Structure):
+    _fields_ = [("lr", _D), ("beta1", _D), ("beta2", _D), ("eps", _D), ("weight_decay", _D)]
+
+
+class DDAdamWState(ctypes.Structure):
+    """The optimizer's device-side state block (``dd_adamw_state_bytes()``)."""
+
+    _fields_ = [("step", ctypes.c_int64), ("beta1_t", _D), ("beta2_t", _D), ("status", _I), ("_pad", _I)]
+
+
+class DDAdamWIO(ctypes.Structure):
+    _fields_ = [("params", ctypes.c_void_p), ("grads", ctypes.c_void_p), ("exp_avg", ctypes.c_void_p),
+                ("exp_avg_sq", ctypes.c_void_p), ("state", ctypes.c_void_p), ("packed", ctypes.c_void_p),
+                ("out_dim", _I), ("compute", _I), ("ln_eps", ctypes.c_float), ("_pad", _I)]
+
+
 def sampling_mode(temperature) -> int:
     """The ``DD_SAMPLE_*`` mode of a notebook ``temperature``: 1 is the plain
     Bernoulli draw, 0 greedy (``probs > 0.5``), any other positive finite value
@@ -282,6 +301,10 @@ EXPORTS = {
     "dd_mlp_backward_workspace": (ctypes.c_int64, []),
     "dd_mlp_backward": (ctypes.c_int, [ctypes.POINTER(DDMlpParams), ctypes.POINTER(DDMlpBackwardIO), ctypes.c_int64,
                                        ctypes.c_void_p, ctypes.c_void_p]),
+    "dd_adamw_state_bytes": (ctypes.c_int64, []),
+    "dd_adamw_init": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p,
+                                     ctypes.c_void_p]),
+    "dd_adamw_step": (ctypes.c_int, [ctypes.POINTER(DDAdamWHyper), ctypes.POINTER(DDAdamWIO), ctypes.c_void_p]),
 }
 
 #: symbols a timing-only lab build (tools/build_variants.sh) or an older
@@ -291,7 +314,8 @@ _LAB_OPTIONAL = ("dd_build_info", "dd_selftest_sqrt", "dd_rollout_kernel", "dd_d
                  "dd_policy_rollout_sampled", "dd_batch_workspace", "dd_batch_plan", "dd_batch_gather",
                  "dd_batch_advantages", "dd_batch_normalize", "dd_episodes_workspace", "dd_episodes_count",
                  "dd_episodes_fill", "dd_episodes_gather", "dd_episodes_advantages", "dd_mlp_evaluate_actions",
-                 "dd_ppo_loss_workspace", "dd_ppo_losses", "dd_mlp_backward_workspace", "dd_mlp_backward")
+                 "dd_ppo_loss_workspace", "dd_ppo_losses", "dd_mlp_backward_workspace", "dd_mlp_backward",
+                 "dd_adamw_state_bytes", "dd_adamw_init", "dd_adamw_step")
 
 
 class NativeLibraryError(RuntimeError):

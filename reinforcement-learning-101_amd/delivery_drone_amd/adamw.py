@@ -1,0 +1,263 @@
+"""The PPO notebook's optimizer steps and its whole PHASE 3, on device.
+
+:class:`AdamW` is ``torch.optim.AdamW`` on an :class:`MlpNet`'s flat parameter
+buffer (``dd_adamw_step``, ``csrc/adamw.hip``): one launch per step that also
+keeps the step count and the bias corrections on the device, so the host
+passes no ``t`` and a captured step can be replayed.  Where the network runs
+``compute="f16x3"`` the kernel applies the operand-range rules of
+``MlpNet.load_state_dict`` to the parameters it is about to write and, if they
+fail, writes nothing but a status bit.  :func:`ppo_update` is the training
+cell's ``for epoch in range(num_epochs)`` loop: :func:`ppo_losses`,
+:meth:`MlpNet.backward` and the two optimizer steps per epoch, with the
+per-epoch logs left on the device.  Nothing here reads back to the host
+unless asked (:meth:`AdamW.status`).
+"""
+from __future__ import annotations
+
+import copy
+import ctypes
+import math
+import struct
+from typing import Dict, Mapping, NamedTuple, Union
+
+import torch
+
+from . import abi
+from .policy import STATE_DICT_KEYS, MlpNet
+from .ppo_loss import ppo_losses
+
+__all__ = ["AdamW", "PpoUpdate", "ppo_update"]
+
+_STATE = struct.Struct("<qddii")  # DDAdamWState
+
+
+class AdamW:
+    """``torch.optim.AdamW(net.parameters(), lr, betas, eps, weight_decay)``
+    for an :class:`MlpNet` (``amsgrad=False``, ``maximize=False``; the
+    defaults are torch's).  It takes :meth:`MlpNet.flat_parameters` and updates
+    that buffer in place; ``exp_avg`` and ``exp_avg_sq`` are float32 buffers of
+    the same length, as torch keeps them.  Each element is evaluated in double
+    and rounded to float32 once (include/dronestep.h)."""
+
+    def __init__(self, net: MlpNet, lr: float = 1e-3, betas=(0.9, 0.999), eps: float = 1e-8,
+                 weight_decay: float = 0.01):
+        if not isinstance(net, MlpNet):
+            raise ValueError("AdamW optimizes an MlpNet")
+        beta1, beta2 = (float(b) for b in betas)
+        for name, x in (("lr", lr), ("eps", eps), ("weight_decay", weight_decay)):
+            self._rate(name, x)
+        for name, b in (("betas[0]", beta1), ("betas[1]", beta2)):
+            if not 0.0 <= b < 1.0:
+                raise ValueError(f"{name} must be in [0, 1), got {b!r}")
+        self.net = net
+        self._lr = float(lr)
+        self.betas, self.eps, self.weight_decay = (beta1, beta2), float(eps), float(weight_decay)
+        self._lib = net._lib
+        if int(self._lib.dd_adamw_state_bytes()) != _STATE.size:
+            raise abi.NativeLibraryError("DDAdamWState: the library's layout is not this module's; rebuild it")
+        self.params = net.flat_parameters()
+        self.exp_avg = torch.empty_like(self.params)
+        self.exp_avg_sq = torch.empty_like(self.params)
+        self._state = torch.empty(_STATE.size // 8, dtype=torch.int64, device=net.device)
+        abi.check(self._lib.dd_adamw_init(self.exp_avg.data_ptr(), self.exp_avg_sq.data_ptr(), self.params.numel(),
+                                          self._state.data_ptr(), net._stream()), "dd_adamw_init")
+
+    @staticmethod
+    def _rate(name, x) -> float:
+        x = float(x)
+        if not (math.isfinite(x) and x >= 0.0):
+            raise ValueError(f"{name} must be finite and not negative, got {x!r}")
+        return x
+
+    @property
+    def lr(self) -> float:
+        return self._lr
+
+    @lr.setter
+    def lr(self, value) -> None:
+        self._lr = self._rate("lr", value)
+
+    def step(self, grads: Union[torch.Tensor, Mapping[str, torch.Tensor]]) -> None:
+        """One optimizer step from ``grads``: the flat gradient buffer, or the
+        dict of views into it that :meth:`MlpNet.backward` returns.  Then
+        ``dd_mlp_pack`` into the network's ``packed`` (same address).  Runs on
+        the current stream and reads nothing back."""
+        net = self.net
+        flat = grads
+        if isinstance(grads, Mapping):  # backward's dict: fourteen views of one flat buffer, in order
+            first = None
+            for k in STATE_DICT_KEYS:
+                t = grads[k]
+                if (not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or not t.is_contiguous()
+                        or t.shape != net._src[k].shape or (first is not None and t.data_ptr() != first)):
+                    raise ValueError("grads must be the flat buffer MlpNet.backward fills, or its dict of views")
+                first = t.data_ptr() + 4 * t.numel()
+            flat = torch.as_strided(grads[STATE_DICT_KEYS[0]], (self.params.numel(),), (1,))
+        if not isinstance(flat, torch.Tensor) or flat.device != net.device:
+            raise ValueError(f"grads must be a tensor on {net.device}")
+        if (tuple(flat.shape) != (self.params.numel(),) or flat.dtype != torch.float32 or not flat.is_contiguous()):
+            raise ValueError(f"grads must be a contiguous float32 tensor of shape ({self.params.numel()},), got "
+                             f"{flat.dtype} {tuple(flat.shape)}")
+        hyper = abi.DDAdamWHyper(self._lr, self.betas[0], self.betas[1], self.eps, self.weight_decay)
+        io = abi.DDAdamWIO(self.params.data_ptr(), flat.data_ptr(), self.exp_avg.data_ptr(),
+                           self.exp_avg_sq.data_ptr(), self._state.data_ptr(), net.packed.data_ptr(), net.out_dim,
+                           net._mode, net.ln_eps, 0)
+        abi.check(self._lib.dd_adamw_step(ctypes.byref(hyper), ctypes.byref(io), net._stream()), "dd_adamw_step")
+
+    # ---- the device state block; each of these is a host read --------------------------
+    def _read_state(self):
+        return _STATE.unpack(self._state.cpu().numpy().tobytes())
+
+    def status(self) -> int:
+        """The sticky status word (``abi.DD_ADAMW_REFUSED``: a step's
+        parameters were not ones ``compute="f16x3"`` can hold, and the step
+        was dropped).  A host read, the only one, and only on request."""
+        return int(self._read_state()[3])
+
+    def step_count(self) -> int:
+        """Steps committed so far (a host read)."""
+        return int(self._read_state()[0])
+
+    def raise_if_refused(self) -> None:
+        """The ``ValueError`` :meth:`MlpNet.load_state_dict` would have raised
+        for the parameters of a refused step."""
+        if self.status() & abi.DD_ADAMW_REFUSED:
+            raise ValueError("AdamW: a step led to parameters that compute='f16x3' cannot hold (it needs finite "
+                             "hidden weights below 2047 in magnitude and LayerNorm outputs below 128) and was "
+                             "dropped; the parameters of the last good step are in place; use compute='f32'")
+
+    # ---- torch's optimizer-state layout ------------------------------------------------
+    def _views(self, flat: torch.Tensor) -> Dict[str, torch.Tensor]:
+        out, first = {}, 0
+        for k in STATE_DICT_KEYS:
+            n = self.net._src[k].numel()
+            out[k] = flat[first:first + n].view(self.net._src[k].shape)
+            first += n
+        return out
+
+    def state_dict(self) -> dict:
+        """``torch.optim.AdamW(...).state_dict()`` for the fourteen parameters
+        in ``STATE_DICT_KEYS`` order (``network.parameters()``' order): per
+        parameter ``step``, ``exp_avg``, ``exp_avg_sq`` (clones), and one
+        param_group, so a torch optimizer over the notebook's module loads it
+        and carries on.  Before the first step the state is empty, as torch's."""
+        group = copy.deepcopy(torch.optim.AdamW([torch.zeros(1)], lr=self._lr, betas=self.betas, eps=self.eps,
+                                                weight_decay=self.weight_decay).state_dict()["param_groups"][0])
+        group["params"] = list(range(len(STATE_DICT_KEYS)))
+        step = self.step_count()
+        state = {}
+        if step > 0:
+            m, v = self._views(self.exp_avg), self._views(self.exp_avg_sq)
+            state = {i: {"step": torch.tensor(float(step)), "exp_avg": m[k].clone(), "exp_avg_sq": v[k].clone()}
+                     for i, k in enumerate(STATE_DICT_KEYS)}
+        return {"state": state, "param_groups": [group]}
+
+    def load_state_dict(self, state_dict: Mapping) -> "AdamW":
+        """Take over from a ``torch.optim.AdamW`` (or an :class:`AdamW`):
+        ``step``, ``exp_avg`` and ``exp_avg_sq`` of the fourteen parameters,
+        and the group's ``lr``, ``betas``, ``eps``, ``weight_decay``.  The
+        running products are rebuilt by ``step`` multiplications, as the
+        kernel forms them; the status word is cleared."""
+        groups = state_dict["param_groups"]
+        if len(groups) != 1 or len(groups[0]["params"]) != len(STATE_DICT_KEYS):
+            raise ValueError("expected one param_group over the network's fourteen parameters")
+        group = groups[0]
+        if group.get("amsgrad") or group.get("maximize"):
+            raise ValueError("amsgrad and maximize are not supported")
+        beta1, beta2 = (float(b) for b in group["betas"])
+        for b in (beta1, beta2):
+            if not 0.0 <= b < 1.0:
+                raise ValueError(f"betas must be in [0, 1), got {group['betas']!r}")
+        lr, eps, wd = (self._rate(k, group[k]) for k in ("lr", "eps", "weight_decay"))
+        state = state_dict["state"]
+        ids = list(group["params"])
+        steps = set()
+        m_new, v_new = torch.zeros_like(self.exp_avg), torch.zeros_like(self.exp_avg_sq)
+        if state:
+            m, v = self._views(m_new), self._views(v_new)
+            for i, k in zip(ids, STATE_DICT_KEYS):
+                s = state[i]
+                if tuple(s["exp_avg"].shape) != tuple(m[k].shape) or tuple(s["exp_avg_sq"].shape) != tuple(m[k].shape):
+                    raise ValueError(f"parameter {i} ({k}): expected shape {tuple(m[k].shape)}")
+                steps.add(int(s["step"]))
+                m[k].copy_(torch.as_tensor(s["exp_avg"]).detach().to(torch.float32))
+                v[k].copy_(torch.as_tensor(s["exp_avg_sq"]).detach().to(torch.float32))
+        if len(steps) > 1:
+            raise ValueError(f"the parameters disagree on the step count: {sorted(steps)}")
+        step = steps.pop() if steps else 0
+        if step < 0:
+            raise ValueError(f"negative step count {step}")
+        b1t = b2t = 1.0
+        for _ in range(step):
+            b1t *= beta1
+            b2t *= beta2
+        self._lr, self.betas, self.eps, self.weight_decay = lr, (beta1, beta2), eps, wd
+        self.exp_avg.copy_(m_new)
+        self.exp_avg_sq.copy_(v_new)
+        block = torch.frombuffer(bytearray(_STATE.pack(step, b1t, b2t, 0, 0)), dtype=torch.int64)
+        self._state.copy_(block)
+        return self
+
+
+class PpoUpdate(NamedTuple):
+    """What the training cell logs after PHASE 3.  ``logs`` maps
+    ``total_loss``, ``policy_loss``, ``value_loss``, ``entropy``,
+    ``ratio_mean``, ``ratio_min``, ``ratio_max``, ``ratio_std``,
+    ``clipped_frac``, ``policy_grad_norm``, ``critic_grad_norm`` to
+    ``[num_epochs]`` float64 device tensors; ``summary`` holds what the cell
+    derives from them, 0-d float64 device tensors."""
+    logs: Dict[str, torch.Tensor]
+    summary: Dict[str, torch.Tensor]
+
+
+LOG_KEYS = ("total_loss", "policy_loss", "value_loss", "entropy", "ratio_mean", "ratio_min", "ratio_max", "ratio_std",
+            "clipped_frac", "policy_grad_norm", "critic_grad_norm")
+
+
+def ppo_update(actor: MlpNet, critic: MlpNet, batch, actor_opt: AdamW, critic_opt: AdamW, *, num_epochs: int = 4,
+               clip_epsilon: float = 0.2, entropy_coef: float = 0.01, value_coef: float = 0.5,
+               max_grad_norm: float = 0.5) -> PpoUpdate:
+    """PHASE 3 of the notebook's training cell: ``num_epochs`` times
+    ``compute_ppo_losses``, ``total_loss.backward()``, the two
+    ``clip_grad_norm_`` and the two optimizer steps, on the full batch (a
+    :class:`PpoBatch`, a :class:`PpoEpisodesBatch`, or the five tensors
+    ``(states, actions, old_log_probs, advantages, returns)``).  Epoch ``e``
+    is exactly ``ppo_grads(...)`` followed by ``actor_opt.step`` and
+    ``critic_opt.step``; one flat gradient buffer per network is reused.
+
+    ``summary``: the epochs' mean of every log under its own name (the cell's
+    ``avg_*``: ``total_loss``, ..., ``ratio_mean``, ``ratio_std``,
+    ``clipped_frac``, the two norms), and ``ratio_min`` = min over epochs,
+    ``ratio_max`` = max over epochs.  Runs on the current stream and reads
+    nothing back for either ``compute``; a refused ``f16x3`` step shows in
+    ``actor_opt.status()`` / ``critic_opt.status()``."""
+    if actor_opt.net is not actor or critic_opt.net is not critic:
+        raise ValueError("actor_opt must optimize actor and critic_opt critic")
+    num_epochs = int(num_epochs)
+    if num_epochs < 1:
+        raise ValueError(f"num_epochs must be at least 1, got {num_epochs}")
+    five = tuple(batch) if isinstance(batch, (tuple, list)) and not hasattr(batch, "_fields") else (batch,)
+    rows = five[0] if isinstance(five[0], torch.Tensor) else five[0].states
+    dev = actor.device
+    scratch = getattr(actor_opt, "_grad_out", None), getattr(critic_opt, "_grad_out", None)
+    if scratch[0] is None:
+        actor_opt._grad_out = torch.empty_like(actor_opt.params)
+    if scratch[1] is None:
+        critic_opt._grad_out = torch.empty_like(critic_opt.params)
+    logs = torch.empty(len(LOG_KEYS), num_epochs, dtype=torch.float64, device=dev)
+    for epoch in range(num_epochs):
+        losses = ppo_losses(actor, critic, *five, clip_epsilon=clip_epsilon, entropy_coef=entropy_coef,
+                            value_coef=value_coef, grads=True)
+        g_actor, n_actor = actor.backward(rows, losses.grad_logits, max_norm=max_grad_norm, out=actor_opt._grad_out)
+        g_critic, n_critic = critic.backward(rows, losses.grad_values, max_norm=max_grad_norm,
+                                             out=critic_opt._grad_out)
+        actor_opt.step(actor_opt._grad_out)
+        critic_opt.step(critic_opt._grad_out)
+        s = losses.ratio_stats
+        logs[:, epoch] = torch.stack([losses.total_loss, losses.policy_loss, losses.value_loss, losses.entropy,
+                                      s["mean"], s["min"], s["max"], s["std"], s["clipped_frac"], n_actor, n_critic])
+    by_key = {k: logs[i] for i, k in enumerate(LOG_KEYS)}
+    summary = {k: v.mean() for k, v in by_key.items()}
+    summary["ratio_min"] = by_key["ratio_min"].min()
+    summary["ratio_max"] = by_key["ratio_max"].max()
+    return PpoUpdate(by_key, summary)

@@ -123,9 +123,46 @@ class MlpNet:
         buffer's size is the same); ``out_dim`` follows, and a launch that
         still asks for the other K gets NaN by the layout tag."""
         src, out_dim = self._validated(state_dict)
-        self._src, self.out_dim = src, out_dim  # kept alive until the pack kernel has read them, as the constructor's
+        if getattr(self, "_flat", None) is not None:
+            # flat_parameters() was handed out: the values go into that buffer, which keeps its address
+            if out_dim != self.out_dim:
+                raise ValueError(f"flat_parameters() fixed the last layer at Linear(64, {self.out_dim}); "
+                                 f"the state_dict has Linear(64, {out_dim})")
+            for k in STATE_DICT_KEYS:
+                self._src[k].copy_(src[k])
+        else:
+            self._src, self.out_dim = src, out_dim  # kept alive until the pack kernel has read them
         self._pack()
         return self
+
+    def flat_parameters(self) -> torch.Tensor:
+        """The fourteen parameter tensors as one flat float32 device buffer in
+        ``STATE_DICT_KEYS`` order (:meth:`grad_numel` elements, the layout of
+        :meth:`backward`'s flat gradient), which an optimizer updates in place
+        (:class:`AdamW`).  The first call copies the parameters into it and
+        re-points the network at views of it, so :meth:`backward` and the next
+        pack read what was written there with no copy; from then on
+        :meth:`load_state_dict` copies into the buffer, so its address stays
+        fixed, and the last layer's width is fixed with it.  After writing the
+        buffer directly, the forward sees the new values once ``packed`` is
+        rebuilt (:class:`AdamW` does that in its step)."""
+        if getattr(self, "_flat", None) is None:
+            flat = torch.empty(self.grad_numel(), dtype=torch.float32, device=self.device)
+            views, first = {}, 0
+            for k in STATE_DICT_KEYS:
+                n = self._src[k].numel()
+                views[k] = flat[first:first + n].view(self._src[k].shape)
+                views[k].copy_(self._src[k])
+                first += n
+            self._src, self._flat = views, flat
+        return self._flat
+
+    def state_dict(self, prefix: str = "network.") -> Dict[str, torch.Tensor]:
+        """Clones of the current float32 parameters under the notebooks' keys
+        (``network.0.weight`` ...), for the training cell's
+        ``torch.save(policy.state_dict(), path)``; :class:`MlpNet`,
+        :meth:`load_state_dict` and the notebooks' ``nn.Module`` load it."""
+        return {prefix + k: self._src[k].clone() for k in STATE_DICT_KEYS}
 
     @classmethod
     def from_file(cls, path: str, **kw) -> "MlpNet":
