@@ -160,6 +160,27 @@ __device__ __forceinline__ void flush_obs_wave(const float* wtile, float* dst, i
     __syncwarp();  // the slice may be rewritten next (rollout frames)
 }
 
+// flush_obs_wave for a wave whose 64 rows all exist and whose dst is 16-byte
+// aligned (the step kernel's usual case; the caller tests both, wave-uniform).
+// The trip count is a constant, so the loop unrolls: the four LDS reads are
+// issued together and the four stores follow, where the general loop's
+// run-time bound made each store wait for its own read in turn, at the very
+// end of the wave's life.
+__device__ __forceinline__ void flush_obs_wave_full(const float* wtile, float* dst) {
+    __syncwarp();
+    const int lane = threadIdx.x & (kWave - 1);
+    constexpr int nv = kWave * DD_OBS_DIM / 4;
+    static_assert(kWave * DD_OBS_DIM % 4 == 0, "a full wave's rows are whole 16-byte vectors");
+    const f32x4* src4 = reinterpret_cast<const f32x4*>(wtile);
+    f32x4* dst4 = reinterpret_cast<f32x4*>(uniform_ptr(dst));
+    // (all four reads into registers of their own before the first store
+    // measured slower than leaving the order to the compiler: -1.0 % against
+    // this loop's -3.1 %, profiles/r13/)
+#pragma unroll
+    for (int k = lane; k < nv; k += kWave) store_nt(dst4, (uint32_t)k, src4[k]);
+    __syncwarp();
+}
+
 template <int AFMT>
 __device__ __forceinline__ uint32_t load_action(const void* actions, uint32_t i) {
     if constexpr (AFMT == DD_ACT_BITMASK) {

@@ -197,8 +197,15 @@ __device__ __forceinline__ void step_tile(const StepArgs& p, const Soa<T>& a, co
     }
     if (p.obs) {  // each wave's 64 rows leave as 16-byte stores
         const uint32_t wrow0 = row0 + (threadIdx.x & ~(kWave - 1));
-        const int rows = (int)min((int64_t)kWave, max((int64_t)0, (int64_t)p.n - wrow0));
-        flush_obs_wave(tile + (threadIdx.x & ~(kWave - 1)) * DD_OBS_DIM, p.obs + (size_t)wrow0 * DD_OBS_DIM, rows);
+        const float* wtile = tile + (threadIdx.x & ~(kWave - 1)) * DD_OBS_DIM;
+        float* dst = p.obs + (size_t)wrow0 * DD_OBS_DIM;
+        // every wave but a ragged batch's last has all 64 rows: the unrolled flush (lane_io.h)
+        if (wrow0 + kWave <= (uint32_t)p.n && (reinterpret_cast<uintptr_t>(p.obs) & 15u) == 0) {
+            flush_obs_wave_full(wtile, dst);
+        } else {
+            const int rows = (int)min((int64_t)kWave, max((int64_t)0, (int64_t)p.n - wrow0));
+            flush_obs_wave(wtile, dst, rows);
+        }
     }
 }
 
