@@ -94,14 +94,6 @@ __device__ __forceinline__ uint32_t given_bits(const void* actions, int32_t fmt,
     return (a[0] != 0.0f ? 1u : 0u) | (a[1] != 0.0f ? 2u : 0u) | (a[2] != 0.0f ? 4u : 0u);
 }
 
-// The batch's sums from the kStatBlocks partials, in every block the same tree.
-__device__ __forceinline__ Part total_of(const Part* __restrict__ part, Part* sh) {
-    static_assert(kStatBlocks == 2 * kBlock, "one pair of partials per thread");
-    Part v = part[threadIdx.x];
-    v += part[threadIdx.x + kBlock];
-    return block_sum<Part>(v, sh);
-}
-
 __global__ __launch_bounds__(kBlock) void ppo_rows_kernel(DDPpoLossIO io, int64_t m, float lo, float hi,
                                                           Part* __restrict__ part) {
     __shared__ Part sh[kBlock];
@@ -144,7 +136,7 @@ __global__ __launch_bounds__(kBlock) void ppo_dev_kernel(const float* __restrict
                                                          double* __restrict__ part_ss) {
     __shared__ Part sh[kBlock];
     __shared__ double shd[kBlock];
-    const double mean = total_of(part, sh).r / (double)m;
+    const double mean = stat_total(part, sh).r / (double)m;
     double s = 0.0;
     for (int64_t k = (int64_t)blockIdx.x * kBlock + threadIdx.x; k < m; k += (int64_t)kStatBlocks * kBlock) {
         const double d = (double)ratio_of(log_prob[k], old_log_prob[k]) - mean;
@@ -160,8 +152,8 @@ __global__ __launch_bounds__(kBlock) void ppo_finish_kernel(const Part* __restri
                                                             double* __restrict__ result) {
     __shared__ Part sh[kBlock];
     __shared__ double shd[kBlock];
-    const Part t = total_of(part, sh);
-    const double ss = block_sum<double>(part_ss[threadIdx.x] + part_ss[threadIdx.x + kBlock], shd);
+    const Part t = stat_total(part, sh);
+    const double ss = stat_total(part_ss, shd);
     if (threadIdx.x != 0) return;
     const double md = (double)m;
     const double policy = -(t.surr / md), value = t.sq / md, entropy = t.ent / (3.0 * md);

@@ -64,26 +64,8 @@ __global__ __launch_bounds__(kBlock) void batch_length_kernel(const uint8_t* __r
 __global__ __launch_bounds__(kScanBlock) void batch_tile_scan_kernel(int64_t* tile_sum, int64_t tiles,
                                                                      int64_t* total) {
     __shared__ int64_t part[kScanBlock];
-    __shared__ int64_t carry;
-    if (threadIdx.x == 0) carry = 0;
-    __syncthreads();
-    for (int64_t base = 0; base < tiles; base += kScanBlock) {
-        const int64_t j = base + threadIdx.x;
-        const int64_t v = j < tiles ? tile_sum[j] : 0;
-        part[threadIdx.x] = v;
-        __syncthreads();
-        for (int off = 1; off < kScanBlock; off <<= 1) {  // Hillis-Steele inclusive scan
-            const int64_t add = threadIdx.x >= (unsigned)off ? part[threadIdx.x - off] : 0;
-            __syncthreads();
-            part[threadIdx.x] += add;
-            __syncthreads();
-        }
-        if (j < tiles) tile_sum[j] = carry + part[threadIdx.x] - v;
-        __syncthreads();
-        if (threadIdx.x == kScanBlock - 1) carry += part[kScanBlock - 1];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) *total = carry;
+    const int64_t m = scan_tile_sums(tile_sum, tiles, part);
+    if (threadIdx.x == 0) *total = m;
 }
 
 // offset[i] = its tile's offset + the exclusive scan of the tile's lengths.
@@ -91,29 +73,25 @@ __global__ __launch_bounds__(kBlock) void batch_offset_kernel(const int32_t* __r
                                                               const int64_t* __restrict__ tile_off, int64_t n,
                                                               int64_t* __restrict__ offset) {
     __shared__ int64_t part[kBlock];
-    const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
-    const int64_t v = i < n ? length[i] : 0;
-    part[threadIdx.x] = v;
-    __syncthreads();
-    for (int off = 1; off < kBlock; off <<= 1) {
-        const int64_t add = threadIdx.x >= (unsigned)off ? part[threadIdx.x - off] : 0;
-        __syncthreads();
-        part[threadIdx.x] += add;
-        __syncthreads();
-    }
-    if (i < n) offset[i] = tile_off[blockIdx.x] + part[threadIdx.x] - v;
+    scan_lane_offsets(length, tile_off, n, offset, part);
 }
 
 // ---------------------------------------------------------------------------
-// Gather.  A block owns kGatherLanes lanes x F frames.  In obs[T][N][15] a
-// frame of the tile is 64 x 60 contiguous bytes (read 16 bytes per thread
-// where the source allows, in the source's 16-byte phase so that LDS stores
-// are aligned too); in states[M][15] a lane's F rows are F x 60 contiguous
-// bytes, written by a group of threads as 16-byte stores on the destination's
-// own 16-byte grid, with 4-byte stores at the two ragged ends.  Frames and
-// lanes past an episode's end are neither read nor written, and a tile with no
-// live frame returns after reading its 64 lengths.
+// Gather.  batch_core.h's gather tile; a lane's rows are the frames before its
+// first episode's end, in place: frame t is row offset[lane] + t.  A tile with
+// no live frame returns after reading its 64 lengths.
 // ---------------------------------------------------------------------------
+template <int F>
+struct FirstEpisodeRows {
+    const int32_t* len_s;  // [kGatherLanes]: the lanes' lengths, 0 past the rollout's edge
+    const int64_t* off_s;  // [kGatherLanes]: and offsets
+    int32_t t0;
+    __device__ __forceinline__ int row(int f, int l) const { return len_s[l] > t0 + f ? f : -1; }
+    __device__ __forceinline__ int count(int l) const { return min(F, len_s[l] - t0); }
+    __device__ __forceinline__ int64_t first(int l) const { return off_s[l] + t0; }
+    __device__ __forceinline__ int frame(int, int r) const { return r; }
+};
+
 template <int F>
 __global__ __launch_bounds__(kBlock) void batch_gather_kernel(const int32_t* __restrict__ length,
                                                               const int64_t* __restrict__ offset,
@@ -123,15 +101,12 @@ __global__ __launch_bounds__(kBlock) void batch_gather_kernel(const int32_t* __r
                                                               float* __restrict__ states, float* __restrict__ act_out,
                                                               float* __restrict__ lp_out, int32_t T, int64_t n,
                                                               int64_t lane_tiles) {
-    constexpr int kGroup = F <= 8 ? 32 : 64;  // threads that write one lane's F rows: (F * 15 + 3) / 4 + 1 float4 at most
-    static_assert((F * DD_OBS_DIM + 3 + 3) / 4 <= kGroup, "a lane's rows of one tile fit one group's stores");
-    constexpr int kSide = kGatherLanes + 1;   // padded [frame][lane] side tiles
     __shared__ __attribute__((aligned(16))) float tile[F * kObsRowPad];
     __shared__ float lp_s[F * kSide];
     __shared__ uint8_t act_s[F * kSide];
     __shared__ int64_t off_s[kGatherLanes];
     __shared__ int32_t len_s[kGatherLanes];
-    __shared__ int32_t ph_s[F];  // each frame's 16-byte phase in obs
+    __shared__ int32_t ph_s[F];
     __shared__ int32_t max_len;
 
     const int tid = (int)threadIdx.x;
@@ -152,86 +127,8 @@ __global__ __launch_bounds__(kBlock) void batch_gather_kernel(const int32_t* __r
     __syncthreads();
     const int nf = min(F, min(max_len, T) - t0);  // frames of this tile that some lane needs
     if (nf <= 0) return;
-
-    if (obs) {
-        const int cnt = lanes * DD_OBS_DIM;
-        for (int f = 0; f < nf; ++f) {
-            const int32_t t = t0 + f;
-            const int64_t first = ((int64_t)t * n + i0) * DD_OBS_DIM;
-            const float* src = obs + first;
-            const int a = ph_s[f];
-            float* dst = tile + f * kObsRowPad + a;
-            const int head = min((4 - a) & 3, cnt);
-            const int nv = (cnt - head) >> 2;
-            const int tail0 = head + (nv << 2);
-            if (tid < nv) {
-                const int e0 = head + (tid << 2);
-                if (len_s[e0 / DD_OBS_DIM] > t || len_s[(e0 + 3) / DD_OBS_DIM] > t)
-                    *reinterpret_cast<f32x4*>(dst + e0) = *reinterpret_cast<const f32x4*>(src + e0);
-            } else if (tid < nv + head) {  // the elements before the first 16-byte boundary
-                const int e = tid - nv;
-                if (len_s[e / DD_OBS_DIM] > t) dst[e] = src[e];
-            } else if (tid < nv + head + (cnt - tail0)) {  // and after the last
-                const int e = tail0 + (tid - nv - head);
-                if (len_s[e / DD_OBS_DIM] > t) dst[e] = src[e];
-            }
-        }
-    }
-    if (actions || log_prob) {
-        for (int idx = tid; idx < nf * kGatherLanes; idx += kBlock) {
-            const int f = idx / kGatherLanes, l = idx % kGatherLanes;
-            if (l < lanes && len_s[l] > t0 + f) {
-                const int64_t o = (int64_t)(t0 + f) * n + i0 + l;
-                if (actions) act_s[f * kSide + l] = actions[o];
-                if (log_prob) lp_s[f * kSide + l] = log_prob[o];
-            }
-        }
-    }
-    __syncthreads();
-
-    if (obs) {
-        const int k = tid % kGroup;
-        for (int l = tid / kGroup; l < lanes; l += kBlock / kGroup) {
-            const int rows = min(F, len_s[l] - t0);
-            if (rows <= 0) continue;
-            const int cnt = rows * DD_OBS_DIM;
-            const int64_t s = (off_s[l] + t0) * DD_OBS_DIM;  // first element of the lane's rows in states
-            const int a = (int)((((uintptr_t)states >> 2) + (uint64_t)s) & 3);
-            const int j0 = (k << 2) - a;  // this thread's four elements: j0 .. j0 + 3 of the lane's cnt
-            if (j0 >= cnt) continue;
-            float v[4];
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                const int j = min(max(j0 + q, 0), cnt - 1);
-                const int f = j / DD_OBS_DIM, c = j % DD_OBS_DIM;
-                v[q] = tile[f * kObsRowPad + ph_s[f] + l * DD_OBS_DIM + c];
-            }
-            float* dst = states + s + j0;
-            if (j0 >= 0 && j0 + 4 <= cnt) {
-                const f32x4 v4 = {v[0], v[1], v[2], v[3]};  // dst is on states' 16-byte grid
-                __builtin_nontemporal_store(v4, reinterpret_cast<f32x4*>(dst));
-            } else {
-#pragma unroll
-                for (int q = 0; q < 4; ++q)
-                    if (j0 + q >= 0 && j0 + q < cnt) dst[q] = v[q];
-            }
-        }
-    }
-    if (actions || log_prob) {
-        for (int idx = tid; idx < kGatherLanes * F; idx += kBlock) {
-            const int l = idx / F, f = idx % F;
-            if (l < lanes && f < nf && len_s[l] > t0 + f) {
-                const int64_t row = off_s[l] + t0 + f;
-                if (log_prob) lp_out[row] = lp_s[f * kSide + l];
-                if (actions) {  // (main, left, right) as Bernoulli.sample() lays them out
-                    const uint32_t bits = act_s[f * kSide + l];
-                    act_out[row * 3 + 0] = (float)(bits & 1u);
-                    act_out[row * 3 + 1] = (float)((bits >> 1) & 1u);
-                    act_out[row * 3 + 2] = (float)((bits >> 2) & 1u);
-                }
-            }
-        }
-    }
+    GatherTile<F>{tile, lp_s, act_s, ph_s, i0, n, t0, lanes, nf}.gather(
+        FirstEpisodeRows<F>{len_s, off_s, t0}, obs, actions, log_prob, states, act_out, lp_out);
 }
 
 // ---------------------------------------------------------------------------
@@ -293,11 +190,6 @@ __global__ __launch_bounds__(kBlock) void batch_adv_kernel(const int32_t* __rest
 // sums of squared deviations; the standard deviation and the output.  No
 // atomics: each element's place in the tree is fixed by m alone.
 // ---------------------------------------------------------------------------
-__device__ __forceinline__ double stat_total(const double* __restrict__ part, double* sh) {
-    static_assert(kStatBlocks == 2 * kBlock, "one pair of partials per thread");
-    return block_sum<double>(part[threadIdx.x] + part[threadIdx.x + kBlock], sh);
-}
-
 __global__ __launch_bounds__(kBlock) void stat_sum_kernel(const float* __restrict__ x, int64_t m,
                                                           double* __restrict__ part_sum) {
     __shared__ double sh[kBlock];
@@ -352,8 +244,7 @@ int64_t dd_batch_workspace(int64_t n) {
 
 int dd_batch_plan(const uint8_t* done, int64_t T, int64_t n, const DDBatchLayout* layout, void* workspace,
                   void* stream) {
-    if (T < 0 || n < 0 || T > INT32_MAX || n > INT32_MAX || !dd::layout_ok(layout) || !workspace ||
-        (T > 0 && n > 0 && !done))
+    if (!dd::shape_ok(T, n) || !dd::layout_ok(layout) || !workspace || (T > 0 && n > 0 && !done))
         return hipErrorInvalidValue;
     hipStream_t s = static_cast<hipStream_t>(stream);
     if (n == 0) return (int)hipMemsetAsync(layout->offset, 0, sizeof(int64_t), s);
@@ -369,43 +260,30 @@ int dd_batch_plan(const uint8_t* done, int64_t T, int64_t n, const DDBatchLayout
 }
 
 int dd_batch_gather(const DDBatchLayout* layout, const DDBatchGatherIO* io, int64_t T, int64_t n, void* stream) {
-    if (T < 0 || n < 0 || T > INT32_MAX || n > INT32_MAX || !dd::layout_ok(layout) || !io) return hipErrorInvalidValue;
-    if ((io->obs != nullptr) != (io->states != nullptr) || (io->actions != nullptr) != (io->actions_out != nullptr) ||
-        (io->log_prob != nullptr) != (io->old_log_probs != nullptr))
-        return hipErrorInvalidValue;
-    const int frames = io->tile_frames == 0 ? 8 : io->tile_frames;
-    if (frames != 8 && frames != 16) return hipErrorInvalidValue;
-    if (T == 0 || n == 0 || (!io->obs && !io->actions && !io->log_prob)) return 0;
-    const int64_t lane_tiles = (n + dd::kGatherLanes - 1) / dd::kGatherLanes;
-    const int64_t blocks = lane_tiles * ((T + frames - 1) / frames);
-    if (blocks > INT32_MAX) return hipErrorInvalidValue;
+    if (!dd::shape_ok(T, n) || !dd::layout_ok(layout) || !io) return hipErrorInvalidValue;
+    dd::GatherLaunch g;
+    if (const int err = dd::gather_launch(io, T, n, true, &g); err || g.blocks == 0) return err;
     hipStream_t s = static_cast<hipStream_t>(stream);
-    dd::with_value<16, 8>(frames, [&](auto f) {
-        hipLaunchKernelGGL(dd::batch_gather_kernel<decltype(f)::value>, dim3((unsigned)blocks), dim3(dd::kBlock), 0, s,
-                           (const int32_t*)layout->length, (const int64_t*)layout->offset, io->obs, io->actions,
-                           io->log_prob, io->states, io->actions_out, io->old_log_probs, (int32_t)T, n, lane_tiles);
+    dd::with_value<16, 8>(g.frames, [&](auto f) {
+        hipLaunchKernelGGL(dd::batch_gather_kernel<decltype(f)::value>, dim3((unsigned)g.blocks), dim3(dd::kBlock), 0,
+                           s, (const int32_t*)layout->length, (const int64_t*)layout->offset, io->obs, io->actions,
+                           io->log_prob, io->states, io->actions_out, io->old_log_probs, (int32_t)T, n, g.lane_tiles);
     });
     return dd::finish();
 }
 
 int dd_batch_advantages(const DDBatchLayout* layout, const DDBatchAdvIO* io, int64_t T, int64_t n, void* stream) {
-    if (T < 0 || n < 0 || T > INT32_MAX || n > INT32_MAX || !dd::layout_ok(layout) || !io) return hipErrorInvalidValue;
-    if (io->mode != DD_BATCH_GAE && io->mode != DD_BATCH_RETURNS) return hipErrorInvalidValue;
-    if (io->precision != DD_F32 && io->precision != DD_F64) return hipErrorInvalidValue;
-    if (io->mode == DD_BATCH_GAE ? (!io->values || !io->advantages) : !io->returns) return hipErrorInvalidValue;
+    if (!dd::shape_ok(T, n) || !dd::layout_ok(layout) || !io) return hipErrorInvalidValue;
+    if (const int err = dd::adv_io_check(io)) return err;
     if (n == 0) return 0;
     if (T > 0 && !io->reward) return hipErrorInvalidValue;
     hipStream_t s = static_cast<hipStream_t>(stream);
-    const float g = (float)io->gamma;
-    const float gl = (float)(io->gamma * io->lambda);
-    dd::with_storage(io->precision, [&](auto tag) {
+    dd::with_adv_kernel(io, [&](auto tag, auto mode, float g, float gl) {
         using R = decltype(tag);
-        dd::with_value<DD_BATCH_GAE, DD_BATCH_RETURNS>(io->mode, [&](auto mode) {
-            hipLaunchKernelGGL((dd::batch_adv_kernel<R, decltype(mode)::value>), dim3((unsigned)dd::tiles_of(n)),
-                               dim3(dd::kBlock), 0, s, (const int32_t*)layout->length, (const int64_t*)layout->offset,
-                               (const uint8_t*)layout->ended, static_cast<const R*>(io->reward), io->values,
-                               io->bootstrap, io->advantages, io->returns, io->episode_return, n, g, gl, io->gamma);
-        });
+        hipLaunchKernelGGL((dd::batch_adv_kernel<R, decltype(mode)::value>), dim3((unsigned)dd::tiles_of(n)),
+                           dim3(dd::kBlock), 0, s, (const int32_t*)layout->length, (const int64_t*)layout->offset,
+                           (const uint8_t*)layout->ended, static_cast<const R*>(io->reward), io->values,
+                           io->bootstrap, io->advantages, io->returns, io->episode_return, n, g, gl, io->gamma);
     });
     return dd::finish();
 }

@@ -96,25 +96,11 @@ __global__ __launch_bounds__(kScanBlock) void episodes_tile_scan_kernel(int64_t*
                                                                         int64_t tiles, int64_t* total_episode,
                                                                         int64_t* total_row, int64_t* totals) {
     __shared__ int64_t part[kScanBlock];
-    __shared__ int64_t carry;
-    for (int pass = 0; pass < 2; ++pass) {
-        int64_t* tile_sum = pass == 0 ? tile_episode : tile_row;
-        if (threadIdx.x == 0) carry = 0;
-        __syncthreads();
-        for (int64_t base = 0; base < tiles; base += kScanBlock) {
-            const int64_t j = base + threadIdx.x;
-            const int64_t v = j < tiles ? tile_sum[j] : 0;
-            const int64_t incl = block_scan_inclusive<kScanBlock>(v, part);
-            if (j < tiles) tile_sum[j] = carry + incl - v;
-            __syncthreads();
-            if (threadIdx.x == kScanBlock - 1) carry += incl;
-            __syncthreads();
-        }
-        if (threadIdx.x == 0) {
-            *(pass == 0 ? total_episode : total_row) = carry;
-            totals[pass] = carry;
-        }
-        __syncthreads();
+    const int64_t e = scan_tile_sums(tile_episode, tiles, part);
+    const int64_t m = scan_tile_sums(tile_row, tiles, part);
+    if (threadIdx.x == 0) {
+        *total_episode = totals[0] = e;
+        *total_row = totals[1] = m;
     }
 }
 
@@ -123,15 +109,8 @@ __global__ __launch_bounds__(kBlock) void episodes_offset_kernel(const int64_t* 
                                                                  const int64_t* __restrict__ tile_row, int64_t n,
                                                                  int64_t* lane_episode, int64_t* lane_row) {
     __shared__ int64_t part[kBlock];
-    const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
-    const int64_t ve = i < n ? lane_episode[i] : 0;
-    const int64_t vr = i < n ? lane_row[i] : 0;
-    const int64_t ie = block_scan_inclusive<kBlock>(ve, part);
-    const int64_t ir = block_scan_inclusive<kBlock>(vr, part);
-    if (i < n) {
-        lane_episode[i] = tile_episode[blockIdx.x] + ie - ve;
-        lane_row[i] = tile_row[blockIdx.x] + ir - vr;
-    }
+    scan_lane_offsets(lane_episode, tile_episode, n, lane_episode, part);
+    scan_lane_offsets(lane_row, tile_row, n, lane_row, part);
 }
 
 // ---------------------------------------------------------------------------
@@ -167,19 +146,28 @@ __global__ __launch_bounds__(kBlock) void episodes_fill_kernel(const uint8_t* __
 }
 
 // ---------------------------------------------------------------------------
-// Gather.  A block owns kGatherLanes lanes x F frames, as batch_gather_kernel
-// does: a frame of the tile is read as 64 x 60 contiguous bytes in the
-// source's 16-byte phase, a lane's rows of the tile leave as one contiguous
-// run on the destination's 16-byte grid.  What differs is which frames are
-// rows.  A lane's kept-frame rank at the tile's first frame is recomputed
-// from done: t0 less the dropped frames before t0, and frame t is dropped
-// exactly when done[t - 1] (done_before for t = 0) is set, so the count is a
-// plain sum of non-zero bytes, split over four threads per lane.  Inside the
-// tile one thread per lane ranks the F frames; a kept frame whose rank is not
-// below the lane's row count belongs to a dropped open episode (the lane's
-// last) and is no row.  rowidx_s[f][lane]: the frame's row within the lane's
-// run of this tile, or -1; rowf_s[lane][r]: the inverse.
+// Gather.  batch_core.h's gather tile; a lane's rows are its kept frames that
+// the layout counted, in frame order from lane_row[lane].  A lane's
+// kept-frame rank at the tile's first frame is recomputed from done: t0 less
+// the dropped frames before t0, and frame t is dropped exactly when
+// done[t - 1] (done_before for t = 0) is set, so the count is a plain sum of
+// non-zero bytes, split over four threads per lane.  Inside the tile one
+// thread per lane ranks the F frames; a kept frame whose rank is not below the
+// lane's row count belongs to a dropped open episode (the lane's last) and is
+// no row.  A tile with no row returns after that.
 // ---------------------------------------------------------------------------
+template <int F>
+struct EpisodeRows {
+    const int8_t* rowidx_s;  // [F][kSide]: the frame's row within the lane's run of this tile, or -1
+    const uint8_t* rowf_s;   // [kGatherLanes][F]: the inverse
+    const int64_t* row0_s;   // [kGatherLanes]: the lane's first row of this tile
+    const int32_t* rows_s;   // [kGatherLanes]: and how many
+    __device__ __forceinline__ int row(int f, int l) const { return rowidx_s[f * kSide + l]; }
+    __device__ __forceinline__ int count(int l) const { return rows_s[l]; }
+    __device__ __forceinline__ int64_t first(int l) const { return row0_s[l]; }
+    __device__ __forceinline__ int frame(int l, int r) const { return rowf_s[l * F + r]; }
+};
+
 template <int F>
 __global__ __launch_bounds__(kBlock) void episodes_gather_kernel(const int64_t* __restrict__ lane_row,
                                                                  const uint8_t* __restrict__ done,
@@ -191,19 +179,16 @@ __global__ __launch_bounds__(kBlock) void episodes_gather_kernel(const int64_t* 
                                                                  float* __restrict__ act_out,
                                                                  float* __restrict__ lp_out, int32_t T, int64_t n,
                                                                  int64_t lane_tiles) {
-    constexpr int kGroup = F <= 8 ? 32 : 64;  // threads that write one lane's rows of the tile
-    static_assert((F * DD_OBS_DIM + 3 + 3) / 4 <= kGroup, "a lane's rows of one tile fit one group's stores");
     static_assert(kBlock == 4 * kGatherLanes, "four threads per lane count the dropped frames");
-    constexpr int kSide = kGatherLanes + 1;   // padded [frame][lane] side tiles
     __shared__ __attribute__((aligned(16))) float tile[F * kObsRowPad];
     __shared__ float lp_s[F * kSide];
     __shared__ uint8_t act_s[F * kSide];
     __shared__ int8_t rowidx_s[F * kSide];
     __shared__ uint8_t rowf_s[kGatherLanes * F];
-    __shared__ int64_t row0_s[kGatherLanes];  // the lane's first row of this tile
-    __shared__ int32_t rows_s[kGatherLanes];  // and how many
+    __shared__ int64_t row0_s[kGatherLanes];
+    __shared__ int32_t rows_s[kGatherLanes];
     __shared__ int32_t part_s[kBlock];
-    __shared__ int32_t ph_s[F];               // each frame's 16-byte phase in obs
+    __shared__ int32_t ph_s[F];
     __shared__ int32_t max_rows;
 
     const int tid = (int)threadIdx.x;
@@ -257,88 +242,8 @@ __global__ __launch_bounds__(kBlock) void episodes_gather_kernel(const int64_t* 
     }
     __syncthreads();
     if (max_rows <= 0) return;  // no row in this tile
-    const int nf = min(F, T - t0);
-
-    if (obs) {
-        const int cnt = lanes * DD_OBS_DIM;
-        for (int f = 0; f < nf; ++f) {
-            const int64_t first = ((int64_t)(t0 + f) * n + i0) * DD_OBS_DIM;
-            const float* src = obs + first;
-            const int a = ph_s[f];
-            float* dst = tile + f * kObsRowPad + a;
-            const int8_t* need = rowidx_s + f * kSide;
-            const int head = min((4 - a) & 3, cnt);
-            const int nv = (cnt - head) >> 2;
-            const int tail0 = head + (nv << 2);
-            if (tid < nv) {
-                const int e0 = head + (tid << 2);
-                if (need[e0 / DD_OBS_DIM] >= 0 || need[(e0 + 3) / DD_OBS_DIM] >= 0)
-                    *reinterpret_cast<f32x4*>(dst + e0) = *reinterpret_cast<const f32x4*>(src + e0);
-            } else if (tid < nv + head) {  // the elements before the first 16-byte boundary
-                const int e = tid - nv;
-                if (need[e / DD_OBS_DIM] >= 0) dst[e] = src[e];
-            } else if (tid < nv + head + (cnt - tail0)) {  // and after the last
-                const int e = tail0 + (tid - nv - head);
-                if (need[e / DD_OBS_DIM] >= 0) dst[e] = src[e];
-            }
-        }
-    }
-    if (actions || log_prob) {
-        for (int idx = tid; idx < nf * kGatherLanes; idx += kBlock) {
-            const int f = idx / kGatherLanes, l = idx % kGatherLanes;
-            if (rowidx_s[f * kSide + l] >= 0) {
-                const int64_t o = (int64_t)(t0 + f) * n + i0 + l;
-                if (actions) act_s[f * kSide + l] = actions[o];
-                if (log_prob) lp_s[f * kSide + l] = log_prob[o];
-            }
-        }
-    }
-    __syncthreads();
-
-    if (obs) {
-        const int k = tid % kGroup;
-        for (int l = tid / kGroup; l < lanes; l += kBlock / kGroup) {
-            const int rows = rows_s[l];
-            if (rows <= 0) continue;
-            const int cnt = rows * DD_OBS_DIM;
-            const int64_t s = row0_s[l] * DD_OBS_DIM;  // first element of the lane's rows in states
-            const int a = (int)((((uintptr_t)states >> 2) + (uint64_t)s) & 3);
-            const int j0 = (k << 2) - a;  // this thread's four elements: j0 .. j0 + 3 of the lane's cnt
-            if (j0 >= cnt) continue;
-            float v[4];
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                const int j = min(max(j0 + q, 0), cnt - 1);
-                const int f = rowf_s[l * F + j / DD_OBS_DIM], c = j % DD_OBS_DIM;
-                v[q] = tile[f * kObsRowPad + ph_s[f] + l * DD_OBS_DIM + c];
-            }
-            float* dst = states + s + j0;
-            if (j0 >= 0 && j0 + 4 <= cnt) {
-                const f32x4 v4 = {v[0], v[1], v[2], v[3]};  // dst is on states' 16-byte grid
-                __builtin_nontemporal_store(v4, reinterpret_cast<f32x4*>(dst));
-            } else {
-#pragma unroll
-                for (int q = 0; q < 4; ++q)
-                    if (j0 + q >= 0 && j0 + q < cnt) dst[q] = v[q];
-            }
-        }
-    }
-    if (actions || log_prob) {
-        for (int idx = tid; idx < kGatherLanes * F; idx += kBlock) {
-            const int l = idx / F, f = idx % F;
-            const int r = rowidx_s[f * kSide + l];
-            if (r >= 0) {
-                const int64_t row = row0_s[l] + r;
-                if (log_prob) lp_out[row] = lp_s[f * kSide + l];
-                if (actions) {  // (main, left, right) as Bernoulli.sample() lays them out
-                    const uint32_t bits = act_s[f * kSide + l];
-                    act_out[row * 3 + 0] = (float)(bits & 1u);
-                    act_out[row * 3 + 1] = (float)((bits >> 1) & 1u);
-                    act_out[row * 3 + 2] = (float)((bits >> 2) & 1u);
-                }
-            }
-        }
-    }
+    GatherTile<F>{tile, lp_s, act_s, ph_s, i0, n, t0, lanes, min(F, T - t0)}.gather(
+        EpisodeRows<F>{rowidx_s, rowf_s, row0_s, rows_s}, obs, actions, log_prob, states, act_out, lp_out);
 }
 
 // ---------------------------------------------------------------------------
@@ -424,7 +329,6 @@ inline bool lanes_ok(const DDEpisodeLayout* lay) { return lay && lay->lane_episo
 inline bool episodes_ok(const DDEpisodeLayout* lay) {
     return lanes_ok(lay) && lay->ep_lane && lay->ep_start && lay->ep_length && lay->ep_ended && lay->ep_offset;
 }
-inline bool shape_ok(int64_t T, int64_t n) { return T >= 0 && n >= 0 && T <= INT32_MAX && n <= INT32_MAX; }
 
 }  // namespace dd
 
@@ -478,21 +382,13 @@ int dd_episodes_fill(const uint8_t* done, const uint8_t* done_before, int64_t T,
 int dd_episodes_gather(const DDEpisodeLayout* layout, const uint8_t* done, const uint8_t* done_before,
                        const DDBatchGatherIO* io, int64_t T, int64_t n, void* stream) {
     if (!dd::shape_ok(T, n) || !dd::lanes_ok(layout) || !io) return hipErrorInvalidValue;
-    if ((io->obs != nullptr) != (io->states != nullptr) || (io->actions != nullptr) != (io->actions_out != nullptr) ||
-        (io->log_prob != nullptr) != (io->old_log_probs != nullptr))
-        return hipErrorInvalidValue;
-    const int frames = io->tile_frames == 0 ? 8 : io->tile_frames;
-    if (frames != 8 && frames != 16) return hipErrorInvalidValue;
-    if (T == 0 || n == 0 || (!io->obs && !io->actions && !io->log_prob)) return 0;
-    if (!done) return hipErrorInvalidValue;
-    const int64_t lane_tiles = (n + dd::kGatherLanes - 1) / dd::kGatherLanes;
-    const int64_t blocks = lane_tiles * ((T + frames - 1) / frames);
-    if (blocks > INT32_MAX) return hipErrorInvalidValue;
+    dd::GatherLaunch g;
+    if (const int err = dd::gather_launch(io, T, n, done != nullptr, &g); err || g.blocks == 0) return err;
     hipStream_t s = static_cast<hipStream_t>(stream);
-    dd::with_value<16, 8>(frames, [&](auto f) {
-        hipLaunchKernelGGL(dd::episodes_gather_kernel<decltype(f)::value>, dim3((unsigned)blocks), dim3(dd::kBlock), 0,
-                           s, (const int64_t*)layout->lane_row, done, done_before, io->obs, io->actions, io->log_prob,
-                           io->states, io->actions_out, io->old_log_probs, (int32_t)T, n, lane_tiles);
+    dd::with_value<16, 8>(g.frames, [&](auto f) {
+        hipLaunchKernelGGL(dd::episodes_gather_kernel<decltype(f)::value>, dim3((unsigned)g.blocks), dim3(dd::kBlock),
+                           0, s, (const int64_t*)layout->lane_row, done, done_before, io->obs, io->actions,
+                           io->log_prob, io->states, io->actions_out, io->old_log_probs, (int32_t)T, n, g.lane_tiles);
     });
     return dd::finish();
 }
@@ -500,24 +396,18 @@ int dd_episodes_gather(const DDEpisodeLayout* layout, const uint8_t* done, const
 int dd_episodes_advantages(const DDEpisodeLayout* layout, const DDBatchAdvIO* io, int64_t T, int64_t n,
                            void* stream) {
     if (!dd::shape_ok(T, n) || !dd::episodes_ok(layout) || !io) return hipErrorInvalidValue;
-    if (io->mode != DD_BATCH_GAE && io->mode != DD_BATCH_RETURNS) return hipErrorInvalidValue;
-    if (io->precision != DD_F32 && io->precision != DD_F64) return hipErrorInvalidValue;
-    if (io->mode == DD_BATCH_GAE ? (!io->values || !io->advantages) : !io->returns) return hipErrorInvalidValue;
+    if (const int err = dd::adv_io_check(io)) return err;
     if (T == 0 || n == 0) return 0;
     if (!io->reward) return hipErrorInvalidValue;
     hipStream_t s = static_cast<hipStream_t>(stream);
-    const float g = (float)io->gamma;
-    const float gl = (float)(io->gamma * io->lambda);
-    dd::with_storage(io->precision, [&](auto tag) {
+    dd::with_adv_kernel(io, [&](auto tag, auto mode, float g, float gl) {
         using R = decltype(tag);
-        dd::with_value<DD_BATCH_GAE, DD_BATCH_RETURNS>(io->mode, [&](auto mode) {
-            hipLaunchKernelGGL((dd::episodes_adv_kernel<R, decltype(mode)::value>), dim3((unsigned)dd::tiles_of(n)),
-                               dim3(dd::kBlock), 0, s, (const int64_t*)layout->lane_episode,
-                               (const int32_t*)layout->ep_start, (const int32_t*)layout->ep_length,
-                               (const uint8_t*)layout->ep_ended, (const int64_t*)layout->ep_offset,
-                               static_cast<const R*>(io->reward), io->values, io->bootstrap, io->advantages,
-                               io->returns, io->episode_return, (int32_t)T, n, g, gl, io->gamma);
-        });
+        hipLaunchKernelGGL((dd::episodes_adv_kernel<R, decltype(mode)::value>), dim3((unsigned)dd::tiles_of(n)),
+                           dim3(dd::kBlock), 0, s, (const int64_t*)layout->lane_episode,
+                           (const int32_t*)layout->ep_start, (const int32_t*)layout->ep_length,
+                           (const uint8_t*)layout->ep_ended, (const int64_t*)layout->ep_offset,
+                           static_cast<const R*>(io->reward), io->values, io->bootstrap, io->advantages, io->returns,
+                           io->episode_return, (int32_t)T, n, g, gl, io->gamma);
     });
     return dd::finish();
 }

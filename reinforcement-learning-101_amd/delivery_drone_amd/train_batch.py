@@ -90,8 +90,13 @@ def _rollout_buffer(t, shape, dtype, dev, what):
     return t.view(torch.uint8) if t.dtype == torch.bool else t
 
 
-class _Plan:
-    """The layout of one rollout's batch and what the later stages need of it."""
+class _PlanBase:
+    """What the two layouts share: the check of ``done``, and gather, advantages
+    and normalize around the subclass's entry points.  A subclass sets
+    ``layout``, ``workspace`` and ``M``, and gives ``_gather(io)`` /
+    ``_advantages(io)`` (the ABI calls), ``_episodes`` (entries of
+    ``episode_return``) and ``_launch_empty`` (whether an ``M == 0`` batch is
+    still launched)."""
 
     def __init__(self, done: torch.Tensor):
         if not isinstance(done, torch.Tensor) or done.dim() != 2:
@@ -103,18 +108,9 @@ class _Plan:
         if not done.is_contiguous():
             raise ValueError("done must be contiguous")
         self.T, self.n = (int(s) for s in done.shape)
-        self.dev = dev = done.device
+        self.dev = done.device
         self.done = done.view(torch.uint8) if done.dtype == torch.bool else done
         self.lib = abi.lib()
-        n = self.n
-        self.lengths = torch.empty(n, dtype=torch.int32, device=dev)
-        self.offsets = torch.empty(n + 1, dtype=torch.int64, device=dev)
-        self.ended = torch.empty(n, dtype=torch.uint8, device=dev)
-        self.workspace = torch.empty(int(self.lib.dd_batch_workspace(n)) // 8, dtype=torch.int64, device=dev)
-        self.layout = abi.DDBatchLayout(self.lengths.data_ptr(), self.offsets.data_ptr(), self.ended.data_ptr())
-        abi.check(self.lib.dd_batch_plan(self.done.data_ptr(), self.T, n, ctypes.byref(self.layout),
-                                         self.workspace.data_ptr(), _stream(dev)), "dd_batch_plan")
-        self.M = int(self.offsets[n].item())  # the one synchronisation: the flat tensors' size
 
     def gather(self, obs, actions, log_prob, tile_frames: int = 0):
         T, n, dev, M = self.T, self.n, self.dev, self.M
@@ -124,10 +120,9 @@ class _Plan:
         states = torch.empty(M, abi.DD_OBS_DIM, dtype=torch.float32, device=dev) if obs is not None else None
         acts = torch.empty(M, 3, dtype=torch.float32, device=dev) if actions is not None else None
         lps = torch.empty(M, dtype=torch.float32, device=dev) if log_prob is not None else None
-        io = abi.DDBatchGatherIO(_ptr(obs), _ptr(actions), _ptr(log_prob), _ptr(states), _ptr(acts), _ptr(lps),
-                                 int(tile_frames), 0)
-        abi.check(self.lib.dd_batch_gather(ctypes.byref(self.layout), ctypes.byref(io), T, n, _stream(dev)),
-                  "dd_batch_gather")
+        if M > 0 or self._launch_empty:
+            self._gather(abi.DDBatchGatherIO(_ptr(obs), _ptr(actions), _ptr(log_prob), _ptr(states), _ptr(acts),
+                                             _ptr(lps), int(tile_frames), 0))
         return states, acts, lps
 
     def advantages(self, reward, mode, gamma, lambda_=0.0, values=None, bootstrap=None):
@@ -137,22 +132,48 @@ class _Plan:
         reward = _rollout_buffer(reward, (T, n), reward.dtype, dev, "reward")
         adv = torch.empty(M, dtype=torch.float32, device=dev) if mode == abi.DD_BATCH_GAE else None
         ret = torch.empty(M, dtype=torch.float32, device=dev)
-        ep = torch.empty(n, dtype=torch.float64, device=dev)
-        io = abi.DDBatchAdvIO(reward.data_ptr(), abi.DD_F64 if reward.dtype == torch.float64 else abi.DD_F32, mode,
-                              _ptr(values), _ptr(bootstrap), _ptr(adv), ret.data_ptr(), ep.data_ptr(),
-                              float(gamma), float(lambda_))
-        abi.check(self.lib.dd_batch_advantages(ctypes.byref(self.layout), ctypes.byref(io), T, n, _stream(dev)),
-                  "dd_batch_advantages")
+        ep = torch.empty(self._episodes, dtype=torch.float64, device=dev)
+        if M > 0 or self._launch_empty:
+            self._advantages(abi.DDBatchAdvIO(reward.data_ptr(),
+                                              abi.DD_F64 if reward.dtype == torch.float64 else abi.DD_F32, mode,
+                                              _ptr(values), _ptr(bootstrap), _ptr(adv), ret.data_ptr(), ep.data_ptr(),
+                                              float(gamma), float(lambda_)))
         return adv, ret, ep
 
     def normalize(self, x: torch.Tensor, normalize: bool):
         """(mean, std, normalised x or x itself)."""
         stats = torch.empty(2, dtype=torch.float64, device=self.dev)
         out = torch.empty_like(x) if normalize else None
-        abi.check(self.lib.dd_batch_normalize(x.data_ptr(), _ptr(out), self.M, stats[0:].data_ptr(),
-                                              stats[1:].data_ptr(), self.workspace.data_ptr(), _stream(self.dev)),
-                  "dd_batch_normalize")
+        abi.check(self.lib.dd_batch_normalize(_ptr(x) if self.M else None, _ptr(out) if self.M else None, self.M,
+                                              stats[0:].data_ptr(), stats[1:].data_ptr(),
+                                              self.workspace.data_ptr(), _stream(self.dev)), "dd_batch_normalize")
         return stats[0], stats[1], out if normalize else x
+
+
+class _Plan(_PlanBase):
+    """The layout of one rollout's batch and what the later stages need of it."""
+    _launch_empty = True
+
+    def __init__(self, done: torch.Tensor):
+        super().__init__(done)
+        n, dev = self.n, self.dev
+        self.lengths = torch.empty(n, dtype=torch.int32, device=dev)
+        self.offsets = torch.empty(n + 1, dtype=torch.int64, device=dev)
+        self.ended = torch.empty(n, dtype=torch.uint8, device=dev)
+        self.workspace = torch.empty(int(self.lib.dd_batch_workspace(n)) // 8, dtype=torch.int64, device=dev)
+        self.layout = abi.DDBatchLayout(self.lengths.data_ptr(), self.offsets.data_ptr(), self.ended.data_ptr())
+        abi.check(self.lib.dd_batch_plan(self.done.data_ptr(), self.T, n, ctypes.byref(self.layout),
+                                         self.workspace.data_ptr(), _stream(dev)), "dd_batch_plan")
+        self.M = int(self.offsets[n].item())  # the one synchronisation: the flat tensors' size
+        self._episodes = n
+
+    def _gather(self, io):
+        abi.check(self.lib.dd_batch_gather(ctypes.byref(self.layout), ctypes.byref(io), self.T, self.n,
+                                           _stream(self.dev)), "dd_batch_gather")
+
+    def _advantages(self, io):
+        abi.check(self.lib.dd_batch_advantages(ctypes.byref(self.layout), ctypes.byref(io), self.T, self.n,
+                                               _stream(self.dev)), "dd_batch_advantages")
 
 
 def _values(critic, rows: torch.Tensor, what: str) -> torch.Tensor:
@@ -271,24 +292,15 @@ class ReinforceEpisodesBatch(NamedTuple):
     lane_row_offsets: torch.Tensor
 
 
-class _EpisodePlan:
+class _EpisodePlan(_PlanBase):
     """The episode layout of one rollout and what the later stages need of it."""
+    _launch_empty = False
 
     def __init__(self, done: torch.Tensor, done_before: Optional[torch.Tensor] = None, drop_open: bool = False):
-        if not isinstance(done, torch.Tensor) or done.dim() != 2:
-            raise ValueError("done must be [T, N]")
-        if done.device.type != "cuda":
-            raise ValueError("training batches are built on the GPU; move the rollout to a CUDA/HIP device")
-        if done.dtype not in (torch.bool, torch.uint8):
-            raise ValueError(f"done must be bool or uint8, got {done.dtype}")
-        if not done.is_contiguous():
-            raise ValueError("done must be contiguous")
-        self.T, self.n = T, n = int(done.shape[0]), int(done.shape[1])
-        self.dev = dev = done.device
-        self.done = done.view(torch.uint8) if done.dtype == torch.bool else done
+        super().__init__(done)
+        T, n, dev, lib = self.T, self.n, self.dev, self.lib
         self.done_before = _rollout_buffer(done_before, (n,), torch.uint8, dev, "done_before")
         self.flags = abi.DD_EPISODES_DROP_OPEN if drop_open else 0
-        self.lib = lib = abi.lib()
         self.lane_episode = torch.empty(n + 1, dtype=torch.int64, device=dev)
         self.lane_row = torch.empty(n + 1, dtype=torch.int64, device=dev)
         totals = torch.empty(2, dtype=torch.int64, device=dev)
@@ -299,6 +311,7 @@ class _EpisodePlan:
                                         ctypes.byref(self.layout), totals.data_ptr(), self.workspace.data_ptr(),
                                         _stream(dev)), "dd_episodes_count")
         self.E, self.M = E, M = tuple(int(v) for v in totals.tolist())  # the one synchronisation: the flat tensors' size
+        self._episodes = E
         self.ep_lane = torch.empty(E, dtype=torch.int32, device=dev)
         self.ep_start = torch.empty(E, dtype=torch.int32, device=dev)
         self.ep_length = torch.empty(E, dtype=torch.int32, device=dev)
@@ -313,46 +326,14 @@ class _EpisodePlan:
             abi.check(lib.dd_episodes_fill(self.done.data_ptr(), _ptr(self.done_before), T, n, self.flags,
                                            ctypes.byref(self.layout), _stream(dev)), "dd_episodes_fill")
 
-    def gather(self, obs, actions, log_prob, tile_frames: int = 0):
-        T, n, dev, M = self.T, self.n, self.dev, self.M
-        obs = _rollout_buffer(obs, (T, n, abi.DD_OBS_DIM), torch.float32, dev, "obs")
-        actions = _rollout_buffer(actions, (T, n), torch.uint8, dev, "actions")
-        log_prob = _rollout_buffer(log_prob, (T, n), torch.float32, dev, "log_prob")
-        states = torch.empty(M, abi.DD_OBS_DIM, dtype=torch.float32, device=dev) if obs is not None else None
-        acts = torch.empty(M, 3, dtype=torch.float32, device=dev) if actions is not None else None
-        lps = torch.empty(M, dtype=torch.float32, device=dev) if log_prob is not None else None
-        if M > 0:
-            io = abi.DDBatchGatherIO(_ptr(obs), _ptr(actions), _ptr(log_prob), _ptr(states), _ptr(acts), _ptr(lps),
-                                     int(tile_frames), 0)
-            abi.check(self.lib.dd_episodes_gather(ctypes.byref(self.layout), self.done.data_ptr(),
-                                                  _ptr(self.done_before), ctypes.byref(io), T, n, _stream(dev)),
-                      "dd_episodes_gather")
-        return states, acts, lps
+    def _gather(self, io):
+        abi.check(self.lib.dd_episodes_gather(ctypes.byref(self.layout), self.done.data_ptr(),
+                                              _ptr(self.done_before), ctypes.byref(io), self.T, self.n,
+                                              _stream(self.dev)), "dd_episodes_gather")
 
-    def advantages(self, reward, mode, gamma, lambda_=0.0, values=None, bootstrap=None):
-        T, n, dev, M, E = self.T, self.n, self.dev, self.M, self.E
-        if not isinstance(reward, torch.Tensor) or reward.dtype not in (torch.float32, torch.float64):
-            raise ValueError("reward must be a float32 or float64 tensor")
-        reward = _rollout_buffer(reward, (T, n), reward.dtype, dev, "reward")
-        adv = torch.empty(M, dtype=torch.float32, device=dev) if mode == abi.DD_BATCH_GAE else None
-        ret = torch.empty(M, dtype=torch.float32, device=dev)
-        ep = torch.empty(E, dtype=torch.float64, device=dev)
-        if M > 0:
-            io = abi.DDBatchAdvIO(reward.data_ptr(), abi.DD_F64 if reward.dtype == torch.float64 else abi.DD_F32,
-                                  mode, _ptr(values), _ptr(bootstrap), _ptr(adv), ret.data_ptr(), ep.data_ptr(),
-                                  float(gamma), float(lambda_))
-            abi.check(self.lib.dd_episodes_advantages(ctypes.byref(self.layout), ctypes.byref(io), T, n,
-                                                      _stream(dev)), "dd_episodes_advantages")
-        return adv, ret, ep
-
-    def normalize(self, x: torch.Tensor, normalize: bool):
-        """(mean, std, normalised x or x itself)."""
-        stats = torch.empty(2, dtype=torch.float64, device=self.dev)
-        out = torch.empty_like(x) if normalize else None
-        abi.check(self.lib.dd_batch_normalize(_ptr(x) if self.M else None, _ptr(out) if self.M else None, self.M,
-                                              stats[0:].data_ptr(), stats[1:].data_ptr(),
-                                              self.workspace.data_ptr(), _stream(self.dev)), "dd_batch_normalize")
-        return stats[0], stats[1], out if normalize else x
+    def _advantages(self, io):
+        abi.check(self.lib.dd_episodes_advantages(ctypes.byref(self.layout), ctypes.byref(io), self.T, self.n,
+                                                  _stream(self.dev)), "dd_episodes_advantages")
 
     def records(self):
         return (self.ep_lane, self.ep_start, self.ep_length, self.ep_offset, self.ep_ended.view(torch.bool))
