@@ -931,6 +931,85 @@ int64_t dd_adamw_state_bytes(void);
 int dd_adamw_init(float *exp_avg, float *exp_avg_sq, int64_t count, DDAdamWState *state, void *stream);
 int dd_adamw_step(const DDAdamWHyper *hyper, const DDAdamWIO *io, void *stream);
 
+/* ---- The REINFORCE and one-step actor-critic losses (additions to ABI 13) ----
+ * The elementwise loss stages of Policy_Gradients.ipynb's and
+ * Actor_Critic_Basic.ipynb's training cells, from per-row network outputs, with
+ * the gradient of each loss at its network's output (csrc/pg_loss.hip's header
+ * has the notebooks' lines and the derivation).  Products and sums are in
+ * double on the float32 inputs, the sums over a reduction tree of fixed shape
+ * (no atomics: the same bits on every run and every device); every per-row
+ * output is rounded to float32 once.
+ *
+ * active (nullable, uint8 [m]; NULL = every row): a row with active == 0 is
+ * out of every mean, its inputs are not read, its gradient rows are exactly 0
+ * and its td_targets / td_errors are 0.  cnt = the number of active rows,
+ * counted on the device.  cnt == 0: the scalars are NaN (torch's mean over no
+ * element), DD_*_COUNT is 0 and every gradient row is 0.
+ *
+ * dd_pg_losses, the score-function loss of both notebooks, from
+ * dd_mlp_evaluate_actions' log_prob [m] and probs [m][3], the given actions and
+ * weights [m] (REINFORCE: the normalised advantages; actor-critic: td_errors):
+ *   result[DD_PG_LOSS]  = -sum_active(log_prob_i w_i) / cnt
+ *   result[DD_PG_COUNT] = cnt
+ *   grad_logits[i][k]   = -(w_i / cnt) (a_ik - p_ik)   at the actor's pre-Sigmoid
+ *       outputs; a factor whose p lies outside [FLT_EPSILON, 1 - FLT_EPSILON]
+ *       gets 0 (clamp_probs passes no gradient there), a NaN p stays NaN
+ * grad_logits needs probs and actions (action_format as DDMlpEvalIO); without
+ * it both may be NULL.
+ *
+ * dd_td_losses, the actor-critic notebook's critic stage, from dd_mlp_forward
+ * of the critic on the states (values) and the next states (next_values), with
+ * rewards and dones (1.0 = the episode ended), all float [m]:
+ *   td_targets[i] = r_i + (gamma v'_i) (1 - d_i)       gamma rounded to float32, as
+ *                   torch multiplies a float32 tensor by a Python number
+ *   td_errors[i]  = delta_i = target_i - v_i           from the unrounded target;
+ *                   these float32 values are dd_pg_losses' weights
+ *   result[DD_TD_MSE]         = sum_active(delta_i^2) / cnt
+ *   result[DD_TD_VALUE_REG]   = value_reg (sum_active(v_i^2) / cnt)
+ *   result[DD_TD_CRITIC_LOSS] = their sum
+ *   result[DD_TD_COUNT]       = cnt
+ *   grad_values[i] = (-2 delta_i + 2 value_reg v_i) / cnt   at the critic's value
+ *       (next_values carries no gradient, as under the notebook's no_grad)
+ *
+ * workspace: dd_pg_loss_workspace() / dd_td_loss_workspace() bytes, 8-byte
+ * aligned.  hipErrorInvalidValue, before any HIP call: a null io, m <= 0, a null
+ * or misaligned workspace, a null required pointer, an unknown action_format,
+ * grad_logits without probs or actions, a gamma or value_reg that is not
+ * finite.  All indices are 64-bit. */
+enum { DD_PG_LOSS = 0, DD_PG_COUNT = 1, DD_PG_RESULTS = 2 };
+typedef struct DDPgLossIO {
+    const float *log_prob;   /* [m]                                            */
+    const float *probs;      /* [m][3]; required with grad_logits              */
+    const void *actions;     /* by action_format; required with grad_logits    */
+    int32_t action_format;   /* DD_ACT_BITMASK or DD_ACT_F32X3                 */
+    int32_t _pad;
+    const float *weights;    /* [m]                                            */
+    const uint8_t *active;   /* nullable [m]                                   */
+    double *result;          /* [DD_PG_RESULTS]                                */
+    float *grad_logits;      /* nullable [m][3]                                */
+} DDPgLossIO;
+
+int64_t dd_pg_loss_workspace(void);
+int dd_pg_losses(const DDPgLossIO *io, int64_t m, void *workspace, void *stream);
+
+enum { DD_TD_CRITIC_LOSS = 0, DD_TD_MSE = 1, DD_TD_VALUE_REG = 2, DD_TD_COUNT = 3, DD_TD_RESULTS = 4 };
+typedef struct DDTdLossIO {
+    const float *values;      /* [m]                                           */
+    const float *next_values; /* [m]                                           */
+    const float *rewards;     /* [m]                                           */
+    const float *dones;       /* [m] 1.0 / 0.0                                 */
+    const uint8_t *active;    /* nullable [m]                                  */
+    double gamma;
+    double value_reg;
+    float *td_targets;        /* [m]                                           */
+    float *td_errors;         /* [m]                                           */
+    double *result;           /* [DD_TD_RESULTS]                               */
+    float *grad_values;       /* nullable [m]                                  */
+} DDTdLossIO;
+
+int64_t dd_td_loss_workspace(void);
+int dd_td_losses(const DDTdLossIO *io, int64_t m, void *workspace, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -61,6 +61,7 @@
 #include <math.h>
 #include <stdint.h>
 
+#include "action_bits.h"
 #include "batch_core.h"
 #include "dronestep.h"
 #include "launch.h"
@@ -86,13 +87,6 @@ struct Part {
 };
 
 __device__ __forceinline__ float ratio_of(float lp, float old) { return (float)exp((double)(lp - old)); }
-
-// Row k's given action as dd_step's bitmask (DDMlpEvalIO's two formats).
-__device__ __forceinline__ uint32_t given_bits(const void* actions, int32_t fmt, int64_t k) {
-    if (fmt == DD_ACT_BITMASK) return static_cast<const uint8_t*>(actions)[k] & 7u;
-    const float* a = static_cast<const float*>(actions) + k * 3;
-    return (a[0] != 0.0f ? 1u : 0u) | (a[1] != 0.0f ? 2u : 0u) | (a[2] != 0.0f ? 4u : 0u);
-}
 
 __global__ __launch_bounds__(kBlock) void ppo_rows_kernel(DDPpoLossIO io, int64_t m, float lo, float hi,
                                                           Part* __restrict__ part) {

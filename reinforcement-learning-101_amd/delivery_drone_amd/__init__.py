@@ -19,7 +19,10 @@ head gradients on such a batch (:func:`ppo_losses`,
 networks' parameter gradients from them (:func:`ppo_grads`,
 :meth:`MlpNet.backward`); and the notebook's two AdamW steps and its whole
 epoch loop on device (:class:`AdamW`, :func:`ppo_update`,
-:meth:`MlpNet.flat_parameters`).
+:meth:`MlpNet.flat_parameters`); and the other two training notebooks'
+learners: REINFORCE (:func:`collect_reinforce`, :func:`reinforce_losses`,
+:func:`reinforce_update`) and the one-step TD actor-critic
+(:func:`td_losses`, :func:`actor_critic_update`).
 """
 from .config import EnvConfig
 from .vec_env import OBS_KEYS, StepInfo, VecDroneEnv
@@ -32,6 +35,8 @@ from .train_batch import collect_ppo_steps, ppo_episodes_batch, reinforce_episod
 from .ppo_loss import PpoLosses, ppo_losses
 from .ppo_grad import PpoGrads, ppo_grads
 from .adamw import AdamW, PpoUpdate, ppo_update
+from .pg_loss import ReinforceLosses, ReinforceUpdate, collect_reinforce, reinforce_losses, reinforce_update
+from .pg_loss import ActorCriticUpdate, TdLosses, actor_critic_update, td_losses
 
 __all__ = [
     "EnvConfig", "VecDroneEnv", "StepInfo", "OBS_KEYS",
@@ -41,5 +46,7 @@ __all__ = [
     "ppo_episodes_batch", "reinforce_episodes_batch", "collect_ppo_steps",
     "ppo_losses", "PpoLosses", "ppo_grads", "PpoGrads",
     "AdamW", "ppo_update", "PpoUpdate",
+    "reinforce_losses", "ReinforceLosses", "reinforce_update", "ReinforceUpdate", "collect_reinforce",
+    "td_losses", "TdLosses", "actor_critic_update", "ActorCriticUpdate",
 ]
 __version__ = "0.1.0"

@@ -25,6 +25,8 @@ __all__ = [
     "DD_PPO_TOTAL_LOSS", "DD_PPO_POLICY_LOSS", "DD_PPO_VALUE_LOSS", "DD_PPO_ENTROPY", "DD_PPO_RATIO_MEAN",
     "DD_PPO_RATIO_MIN", "DD_PPO_RATIO_MAX", "DD_PPO_RATIO_STD", "DD_PPO_CLIPPED_FRAC", "DD_PPO_RESULTS",
     "DD_ADAMW_REFUSED", "DDAdamWHyper", "DDAdamWState", "DDAdamWIO",
+    "DD_PG_LOSS", "DD_PG_COUNT", "DD_PG_RESULTS", "DDPgLossIO",
+    "DD_TD_CRITIC_LOSS", "DD_TD_MSE", "DD_TD_VALUE_REG", "DD_TD_COUNT", "DD_TD_RESULTS", "DDTdLossIO",
     "sampling_mode", "lib", "load", "library_path", "check",
     "NativeLibraryError",
 ]
@@ -48,6 +50,8 @@ DD_EPISODES_DROP_OPEN = 1
  DD_PPO_RATIO_MAX, DD_PPO_RATIO_STD, DD_PPO_CLIPPED_FRAC, DD_PPO_RESULTS) = range(10)
 
 DD_ADAMW_REFUSED = 1
+DD_PG_LOSS, DD_PG_COUNT, DD_PG_RESULTS = range(3)
+DD_TD_CRITIC_LOSS, DD_TD_MSE, DD_TD_VALUE_REG, DD_TD_COUNT, DD_TD_RESULTS = range(5)
 
 _D = ctypes.c_double
 _I = ctypes.c_int32
@@ -213,6 +217,19 @@ class DDAdamWIO(ctypes.Structure):
                 ("out_dim", _I), ("compute", _I), ("ln_eps", ctypes.c_float), ("_pad", _I)]
 
 
+class DDPgLossIO(ctypes.Structure):
+    _fields_ = [("log_prob", ctypes.c_void_p), ("probs", ctypes.c_void_p), ("actions", ctypes.c_void_p),
+                ("action_format", _I), ("_pad", _I), ("weights", ctypes.c_void_p), ("active", ctypes.c_void_p),
+                ("result", ctypes.c_void_p), ("grad_logits", ctypes.c_void_p)]
+
+
+class DDTdLossIO(ctypes.Structure):
+    _fields_ = [("values", ctypes.c_void_p), ("next_values", ctypes.c_void_p), ("rewards", ctypes.c_void_p),
+                ("dones", ctypes.c_void_p), ("active", ctypes.c_void_p), ("gamma", _D), ("value_reg", _D),
+                ("td_targets", ctypes.c_void_p), ("td_errors", ctypes.c_void_p), ("result", ctypes.c_void_p),
+                ("grad_values", ctypes.c_void_p)]
+
+
 def sampling_mode(temperature) -> int:
     """The ``DD_SAMPLE_*`` mode of a notebook ``temperature``: 1 is the plain
     Bernoulli draw, 0 greedy (``probs > 0.5``), any other positive finite value
@@ -305,6 +322,10 @@ EXPORTS = {
     "dd_adamw_init": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p,
                                      ctypes.c_void_p]),
     "dd_adamw_step": (ctypes.c_int, [ctypes.POINTER(DDAdamWHyper), ctypes.POINTER(DDAdamWIO), ctypes.c_void_p]),
+    "dd_pg_loss_workspace": (ctypes.c_int64, []),
+    "dd_pg_losses": (ctypes.c_int, [ctypes.POINTER(DDPgLossIO), ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p]),
+    "dd_td_loss_workspace": (ctypes.c_int64, []),
+    "dd_td_losses": (ctypes.c_int, [ctypes.POINTER(DDTdLossIO), ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p]),
 }
 
 #: symbols a timing-only lab build (tools/build_variants.sh) or an older
@@ -315,7 +336,8 @@ _LAB_OPTIONAL = ("dd_build_info", "dd_selftest_sqrt", "dd_rollout_kernel", "dd_d
                  "dd_batch_advantages", "dd_batch_normalize", "dd_episodes_workspace", "dd_episodes_count",
                  "dd_episodes_fill", "dd_episodes_gather", "dd_episodes_advantages", "dd_mlp_evaluate_actions",
                  "dd_ppo_loss_workspace", "dd_ppo_losses", "dd_mlp_backward_workspace", "dd_mlp_backward",
-                 "dd_adamw_state_bytes", "dd_adamw_init", "dd_adamw_step")
+                 "dd_adamw_state_bytes", "dd_adamw_init", "dd_adamw_step", "dd_pg_loss_workspace", "dd_pg_losses",
+                 "dd_td_loss_workspace", "dd_td_losses")
 
 
 class NativeLibraryError(RuntimeError):
