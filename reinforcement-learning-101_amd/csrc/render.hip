@@ -21,8 +21,9 @@
 //   * filled circle (c, r): (X - cx)^2 + (Y - cy)^2 <= r^2; filled ellipse in
 //     rect (l, t, w, h): pixel centres inside the inscribed ellipse;
 //   * transform.rotate(surface, -angle) + blit centred on (x, y): every pixel
-//     centre is rotated back into the 40 x 20 drone sprite and takes the
-//     sprite pixel it lands on (nearest neighbour), transparent outside;
+//     centre is rotated back into the drone sprite (40 wide, twice
+//     drone_half_height high: 40 x 20) and takes the sprite pixel it lands
+//     on (nearest neighbour), transparent outside;
 //   * text: pygame.font.Font(None, 24 | 30 | 48) is stood in for by DejaVu
 //     Sans Bold at 16 / 20 / 33 px (font_atlas.h); anti-aliased glyph
 //     coverage a blends as pygame's ALPHA_BLEND: d += ((s - d) * a + s) >> 8;
@@ -246,14 +247,20 @@ __global__ __launch_bounds__(kBlock) void render_kernel(Args p, View<T> v) {
     const bool hud = p.flags & DD_RENDER_HUD;
     const bool over = (p.flags & DD_RENDER_GAME_OVER) && (status & DD_ST_DONE);
 
-    // Block culling: a block covers 8,192 consecutive pixels (11-12 rows),
+    // Block culling: a block covers 8,192 consecutive pixels (11-12 rows at 800 wide),
     // so each group of primitives is tested against the block's rows once
     // (a scalar branch) and most blocks only fill sky or ground.
     //   pad band: the platform and its centre line (pt .. bottom);
-    //   drone band: the sprite (radius 22.4) and the flames (<= 30 px out);
+    //   drone band: pixel centres within `reach` rows of y.  The sprite's
+    //     corners are sqrt(hw^2 + hh^2) <= hw + hh out; the main flame's
+    //     centre is hh + 7.5 out, truncated to int (< 1 row, up or down),
+    //     and its ellipse 7.5 rows more; a side flame's centre is hw + 5
+    //     out, truncated, its circle 5 rows more, and its rows are whole
+    //     numbers where the band measures from pixel centres (0.5);
     //   strings: only those whose rows meet the block's are laid out.
     const bool blk_pad = row_hi >= pt && row_lo <= pby;
-    const bool blk_drone = (float)row_hi + 48.0f >= yf && (float)row_lo - 48.0f <= yf;
+    const float reach = fmaxf(hw + hh + 1.0f, fmaxf(hh + 7.5f + 8.0f + 1.0f, hw + 5.0f + 5.0f + 1.5f));
+    const bool blk_drone = ((float)row_hi + 0.5f) - yf >= -reach && ((float)row_lo + 0.5f) - yf <= reach;
     // string k: where (y0 follows from the face height alone) and whether it is drawn
     int tx[kTexts], ty[kTexts], tface[kTexts];
     bool ton[kTexts], tcentre[kTexts];
@@ -403,7 +410,7 @@ __global__ __launch_bounds__(kBlock) void render_kernel(Args p, View<T> v) {
             }
         }
         draw_texts(px4, need & 0x40u, texts, colchar, fl, raster, X0, Y);  // the pad's "H"
-        if (blk_drone && fabsf(((float)Y + 0.5f) - yf) <= hw + hh + 1.0f) {
+        if (blk_drone && fabsf(((float)Y + 0.5f) - yf) <= reach) {
 #pragma unroll
             for (int j = 0; j < kPix; ++j) {
                 const int X = X0 + j;
@@ -435,7 +442,8 @@ __global__ __launch_bounds__(kBlock) void render_kernel(Args p, View<T> v) {
 #pragma unroll
             for (int j = 0; j < kPix; ++j) {
                 const int X = X0 + j;
-                if (X >= 10 && X < 210) px4[j] = X < 10 + fuel_w ? fuel_color : kBarBg;
+                // the fill is a rect of its own, (10, 10, fuel_w, 20): past the background's end when fuel > max
+                if (X >= 10 && (X < 210 || X - 10 < fuel_w)) px4[j] = X - 10 < fuel_w ? fuel_color : kBarBg;
             }
         }
         draw_texts(px4, need & 0x3Fu, texts, colchar, fl, raster, X0, Y);
