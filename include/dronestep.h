@@ -1010,6 +1010,53 @@ typedef struct DDTdLossIO {
 int64_t dd_td_loss_workspace(void);
 int dd_td_losses(const DDTdLossIO *io, int64_t m, void *workspace, void *stream);
 
+/* ---- Shuffled minibatch epochs: a keyed permutation of rows (additions to ABI 13) ----
+ * perm(j), j in [0, m), is a stateless bijection of [0, m) that depends on
+ * (m, seed, epoch) alone: every thread computes it for its own j, so there is
+ * no sort, no atomic, no workspace, and launch geometry or sharding cannot
+ * change it.  The definition (tests/shuffle_ref.py restates it in NumPy):
+ *   b = bit_length(m - 1) (0 for m == 1);  h = max(1, ceil(b / 2));  mask = 2^h - 1
+ *   cipher(x), on the domain [0, 2^(2h)), m <= 2^(2h) < 4 m for m >= 2:
+ *     (L, R) = (x >> h, x & mask); for r = 0 .. 7:
+ *       F = philox4x32_10(counter = (R, r, epoch_lo, epoch_hi ^ 0xC3C3C3C3),
+ *                         key = (seed_lo, seed_hi))[0] & mask
+ *       (L, R) = (R, L ^ F)
+ *     cipher(x) = (L << h) | R          a balanced Feistel network: a bijection
+ *   perm(j): x = j; do x = cipher(x) while x >= m      cycle walking: j < m lies on
+ *     a cycle of the cipher, which re-enters [0, m) at the latest at j itself
+ * dd_shuffle_indices: out[j] = perm(j).
+ * dd_shuffle_rows: dst[j] = src[perm(j)] for the columns of a training batch,
+ * moved as bits (NaN payloads survive).  Every column is a (source,
+ * destination) pair that is null together; indices (nullable) also receives
+ * perm.  Sources and destinations need 4-byte alignment only (1 for uint8
+ * actions).  It cannot run in place.
+ * Both are asynchronous on the stream, allocate nothing and read nothing back;
+ * a captured launch replays the permutation of the (seed, epoch) it was
+ * captured with.
+ * hipErrorInvalidValue, before any launch: m < 0 or m >= 2^31, a null io (or
+ * out), a column with one of its two pointers null, actions with an
+ * action_format other than DD_ACT_BITMASK or DD_ACT_F32X3, a destination
+ * range that overlaps a source range.  m == 0 (or no column at all): 0, no
+ * launch. */
+typedef struct DDShuffleIO {
+    const float *states;         /* [m][15]                                   */
+    const void *actions;         /* uint8 [m] or float [m][3], action_format  */
+    const float *old_log_probs;  /* [m]                                       */
+    const float *advantages;     /* [m]                                       */
+    const float *returns;        /* [m]                                       */
+    int32_t action_format;       /* DD_ACT_BITMASK or DD_ACT_F32X3            */
+    int32_t _pad;
+    float *states_out;           /* each null exactly when its source is      */
+    void *actions_out;
+    float *old_log_probs_out;
+    float *advantages_out;
+    float *returns_out;
+    int32_t *indices;            /* nullable [m]: perm                        */
+} DDShuffleIO;
+
+int dd_shuffle_indices(int64_t m, uint64_t seed, uint64_t epoch, int32_t *out, void *stream);
+int dd_shuffle_rows(const DDShuffleIO *io, int64_t m, uint64_t seed, uint64_t epoch, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

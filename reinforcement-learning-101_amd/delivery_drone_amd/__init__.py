@@ -19,7 +19,9 @@ head gradients on such a batch (:func:`ppo_losses`,
 networks' parameter gradients from them (:func:`ppo_grads`,
 :meth:`MlpNet.backward`); and the notebook's two AdamW steps and its whole
 epoch loop on device (:class:`AdamW`, :func:`ppo_update`,
-:meth:`MlpNet.flat_parameters`); and the other two training notebooks'
+:meth:`MlpNet.flat_parameters`), full-batch or in shuffled minibatches
+(:func:`shuffle_batch`, :func:`shuffle_indices`: a keyed permutation computed
+on device); and the other two training notebooks'
 learners: REINFORCE (:func:`collect_reinforce`, :func:`reinforce_losses`,
 :func:`reinforce_update`) and the one-step TD actor-critic
 (:func:`td_losses`, :func:`actor_critic_update`).
@@ -34,6 +36,7 @@ from .train_batch import collect_ppo, ppo_batch, reinforce_batch
 from .train_batch import collect_ppo_steps, ppo_episodes_batch, reinforce_episodes_batch
 from .ppo_loss import PpoLosses, ppo_losses
 from .ppo_grad import PpoGrads, ppo_grads
+from .shuffle import ShuffledBatch, shuffle_batch, shuffle_indices
 from .adamw import AdamW, PpoUpdate, ppo_update
 from .pg_loss import ReinforceLosses, ReinforceUpdate, collect_reinforce, reinforce_losses, reinforce_update
 from .pg_loss import ActorCriticUpdate, TdLosses, actor_critic_update, td_losses
@@ -46,6 +49,7 @@ __all__ = [
     "ppo_episodes_batch", "reinforce_episodes_batch", "collect_ppo_steps",
     "ppo_losses", "PpoLosses", "ppo_grads", "PpoGrads",
     "AdamW", "ppo_update", "PpoUpdate",
+    "shuffle_batch", "shuffle_indices", "ShuffledBatch",
     "reinforce_losses", "ReinforceLosses", "reinforce_update", "ReinforceUpdate", "collect_reinforce",
     "td_losses", "TdLosses", "actor_critic_update", "ActorCriticUpdate",
 ]

@@ -27,6 +27,7 @@ __all__ = [
     "DD_ADAMW_REFUSED", "DDAdamWHyper", "DDAdamWState", "DDAdamWIO",
     "DD_PG_LOSS", "DD_PG_COUNT", "DD_PG_RESULTS", "DDPgLossIO",
     "DD_TD_CRITIC_LOSS", "DD_TD_MSE", "DD_TD_VALUE_REG", "DD_TD_COUNT", "DD_TD_RESULTS", "DDTdLossIO",
+    "DDShuffleIO",
     "sampling_mode", "lib", "load", "library_path", "check",
     "NativeLibraryError",
 ]
@@ -230,6 +231,14 @@ class DDTdLossIO(ctypes.Structure):
                 ("grad_values", ctypes.c_void_p)]
 
 
+class DDShuffleIO(ctypes.Structure):
+    _fields_ = [("states", ctypes.c_void_p), ("actions", ctypes.c_void_p), ("old_log_probs", ctypes.c_void_p),
+                ("advantages", ctypes.c_void_p), ("returns", ctypes.c_void_p), ("action_format", _I), ("_pad", _I),
+                ("states_out", ctypes.c_void_p), ("actions_out", ctypes.c_void_p),
+                ("old_log_probs_out", ctypes.c_void_p), ("advantages_out", ctypes.c_void_p),
+                ("returns_out", ctypes.c_void_p), ("indices", ctypes.c_void_p)]
+
+
 def sampling_mode(temperature) -> int:
     """The ``DD_SAMPLE_*`` mode of a notebook ``temperature``: 1 is the plain
     Bernoulli draw, 0 greedy (``probs > 0.5``), any other positive finite value
@@ -326,6 +335,10 @@ EXPORTS = {
     "dd_pg_losses": (ctypes.c_int, [ctypes.POINTER(DDPgLossIO), ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p]),
     "dd_td_loss_workspace": (ctypes.c_int64, []),
     "dd_td_losses": (ctypes.c_int, [ctypes.POINTER(DDTdLossIO), ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p]),
+    "dd_shuffle_indices": (ctypes.c_int, [ctypes.c_int64, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_void_p,
+                                          ctypes.c_void_p]),
+    "dd_shuffle_rows": (ctypes.c_int, [ctypes.POINTER(DDShuffleIO), ctypes.c_int64, ctypes.c_uint64, ctypes.c_uint64,
+                                       ctypes.c_void_p]),
 }
 
 #: symbols a timing-only lab build (tools/build_variants.sh) or an older
@@ -337,7 +350,7 @@ _LAB_OPTIONAL = ("dd_build_info", "dd_selftest_sqrt", "dd_rollout_kernel", "dd_d
                  "dd_episodes_fill", "dd_episodes_gather", "dd_episodes_advantages", "dd_mlp_evaluate_actions",
                  "dd_ppo_loss_workspace", "dd_ppo_losses", "dd_mlp_backward_workspace", "dd_mlp_backward",
                  "dd_adamw_state_bytes", "dd_adamw_init", "dd_adamw_step", "dd_pg_loss_workspace", "dd_pg_losses",
-                 "dd_td_loss_workspace", "dd_td_losses")
+                 "dd_td_loss_workspace", "dd_td_losses", "dd_shuffle_indices", "dd_shuffle_rows")
 
 
 class NativeLibraryError(RuntimeError):

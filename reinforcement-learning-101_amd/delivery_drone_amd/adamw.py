@@ -18,13 +18,15 @@ import copy
 import ctypes
 import math
 import struct
-from typing import Dict, Mapping, NamedTuple, Union
+from typing import Dict, Mapping, NamedTuple, Optional, Union
 
 import torch
 
 from . import abi
 from .policy import STATE_DICT_KEYS, MlpNet
 from .ppo_loss import ppo_losses
+from .shuffle import shuffle_batch
+from .train_batch import PpoBatch, PpoEpisodesBatch
 
 __all__ = ["AdamW", "PpoUpdate", "ppo_update"]
 
@@ -204,8 +206,9 @@ class PpoUpdate(NamedTuple):
     ``total_loss``, ``policy_loss``, ``value_loss``, ``entropy``,
     ``ratio_mean``, ``ratio_min``, ``ratio_max``, ``ratio_std``,
     ``clipped_frac``, ``policy_grad_norm``, ``critic_grad_norm`` to
-    ``[num_epochs]`` float64 device tensors; ``summary`` holds what the cell
-    derives from them, 0-d float64 device tensors."""
+    ``[num_epochs]`` float64 device tensors (``[num_epochs, n_minibatches]``
+    with ``minibatch_size``); ``summary`` holds what the cell derives from
+    them, 0-d float64 device tensors."""
     logs: Dict[str, torch.Tensor]
     summary: Dict[str, torch.Tensor]
 
@@ -214,9 +217,18 @@ LOG_KEYS = ("total_loss", "policy_loss", "value_loss", "entropy", "ratio_mean", 
             "clipped_frac", "policy_grad_norm", "critic_grad_norm")
 
 
+def minibatch_ranges(m: int, size: int, drop_last: bool = False):
+    """The row ranges ``[lo, hi)`` of an epoch's minibatches over ``m``
+    shuffled rows: ``[i size, min((i + 1) size, m))``, without the tail shorter
+    than ``size`` when ``drop_last``."""
+    stop = m - m % size if drop_last else m
+    return [(lo, min(lo + size, m)) for lo in range(0, stop, size)]
+
+
 def ppo_update(actor: MlpNet, critic: MlpNet, batch, actor_opt: AdamW, critic_opt: AdamW, *, num_epochs: int = 4,
                clip_epsilon: float = 0.2, entropy_coef: float = 0.01, value_coef: float = 0.5,
-               max_grad_norm: float = 0.5) -> PpoUpdate:
+               max_grad_norm: float = 0.5, minibatch_size: Optional[int] = None, shuffle_seed: int = 0,
+               shuffle_epoch: int = 0, drop_last: bool = False) -> PpoUpdate:
     """PHASE 3 of the notebook's training cell: ``num_epochs`` times
     ``compute_ppo_losses``, ``total_loss.backward()``, the two
     ``clip_grad_norm_`` and the two optimizer steps, on the full batch (a
@@ -225,10 +237,25 @@ def ppo_update(actor: MlpNet, critic: MlpNet, batch, actor_opt: AdamW, critic_op
     is exactly ``ppo_grads(...)`` followed by ``actor_opt.step`` and
     ``critic_opt.step``; one flat gradient buffer per network is reused.
 
-    ``summary``: the epochs' mean of every log under its own name (the cell's
+    ``minibatch_size=B`` (default ``None``: the full batch, as above) runs the
+    notebook's "shuffle collected data into minibatches / for each minibatch":
+    at epoch ``e`` the batch is shuffled on device with the key
+    ``(shuffle_seed, shuffle_epoch + e)`` (:func:`shuffle_batch`, into buffers
+    allocated once per call), and each row range ``[i B, min((i + 1) B, M))``
+    of the shuffled batch is one minibatch: ``ppo_grads`` on that range, then
+    the two optimizer steps.  The tail shorter than ``B`` is a minibatch of its
+    own unless ``drop_last``.  Advantages stay as the batch has them
+    (normalised over the whole batch by the batch builders), not re-normalised
+    per minibatch.  ``logs[k]`` is then ``[num_epochs, n_minibatches]``.
+    ``shuffle_epoch`` is a host integer: pass a different one on every call
+    (for instance ``update * num_epochs``) or every call repeats the same
+    permutations, and a captured graph replays the permutations it was
+    captured with.
+
+    ``summary``: the steps' mean of every log under its own name (the cell's
     ``avg_*``: ``total_loss``, ..., ``ratio_mean``, ``ratio_std``,
-    ``clipped_frac``, the two norms), and ``ratio_min`` = min over epochs,
-    ``ratio_max`` = max over epochs.  Runs on the current stream and reads
+    ``clipped_frac``, the two norms), and ``ratio_min`` = min over all steps,
+    ``ratio_max`` = max over all steps.  Runs on the current stream and reads
     nothing back for either ``compute``; a refused ``f16x3`` step shows in
     ``actor_opt.status()`` / ``critic_opt.status()``."""
     if actor_opt.net is not actor or critic_opt.net is not critic:
@@ -237,15 +264,16 @@ def ppo_update(actor: MlpNet, critic: MlpNet, batch, actor_opt: AdamW, critic_op
     if num_epochs < 1:
         raise ValueError(f"num_epochs must be at least 1, got {num_epochs}")
     five = tuple(batch) if isinstance(batch, (tuple, list)) and not hasattr(batch, "_fields") else (batch,)
-    rows = five[0] if isinstance(five[0], torch.Tensor) else five[0].states
     dev = actor.device
     scratch = getattr(actor_opt, "_grad_out", None), getattr(critic_opt, "_grad_out", None)
     if scratch[0] is None:
         actor_opt._grad_out = torch.empty_like(actor_opt.params)
     if scratch[1] is None:
         critic_opt._grad_out = torch.empty_like(critic_opt.params)
-    logs = torch.empty(len(LOG_KEYS), num_epochs, dtype=torch.float64, device=dev)
-    for epoch in range(num_epochs):
+
+    def step(five):
+        """One optimizer step of each network on the rows of ``five``; its log entries."""
+        rows = five[0] if isinstance(five[0], torch.Tensor) else five[0].states
         losses = ppo_losses(actor, critic, *five, clip_epsilon=clip_epsilon, entropy_coef=entropy_coef,
                             value_coef=value_coef, grads=True)
         g_actor, n_actor = actor.backward(rows, losses.grad_logits, max_norm=max_grad_norm, out=actor_opt._grad_out)
@@ -254,8 +282,33 @@ def ppo_update(actor: MlpNet, critic: MlpNet, batch, actor_opt: AdamW, critic_op
         actor_opt.step(actor_opt._grad_out)
         critic_opt.step(critic_opt._grad_out)
         s = losses.ratio_stats
-        logs[:, epoch] = torch.stack([losses.total_loss, losses.policy_loss, losses.value_loss, losses.entropy,
-                                      s["mean"], s["min"], s["max"], s["std"], s["clipped_frac"], n_actor, n_critic])
+        return torch.stack([losses.total_loss, losses.policy_loss, losses.value_loss, losses.entropy,
+                            s["mean"], s["min"], s["max"], s["std"], s["clipped_frac"], n_actor, n_critic])
+
+    if minibatch_size is None:
+        logs = torch.empty(len(LOG_KEYS), num_epochs, dtype=torch.float64, device=dev)
+        for epoch in range(num_epochs):
+            logs[:, epoch] = step(five)
+    else:
+        size = int(minibatch_size)
+        if size < 1:
+            raise ValueError(f"minibatch_size must be at least 1, got {minibatch_size!r}")
+        if len(five) == 1:  # a batch: its five tensors
+            if not isinstance(five[0], (PpoBatch, PpoEpisodesBatch)):
+                raise ValueError("batch must be a PpoBatch, a PpoEpisodesBatch or the five tensors")
+            five = tuple(five[0][:5])
+        if len(five) != 5 or not all(isinstance(t, torch.Tensor) for t in five):
+            raise ValueError("minibatches need all five tensors (states, actions, old_log_probs, advantages, returns)")
+        m = int(five[0].shape[0])
+        ranges = minibatch_ranges(m, size, drop_last)
+        if not ranges:
+            raise ValueError(f"no minibatch to step on: {m} rows, minibatch_size {size}, drop_last={bool(drop_last)}")
+        logs = torch.empty(len(LOG_KEYS), num_epochs, len(ranges), dtype=torch.float64, device=dev)
+        shuffled = None
+        for epoch in range(num_epochs):
+            shuffled = shuffle_batch(five, seed=shuffle_seed, epoch=int(shuffle_epoch) + epoch, out=shuffled)
+            for i, (lo, hi) in enumerate(ranges):
+                logs[:, epoch, i] = step(tuple(t[lo:hi] for t in shuffled[:5]))
     by_key = {k: logs[i] for i, k in enumerate(LOG_KEYS)}
     summary = {k: v.mean() for k, v in by_key.items()}
     summary["ratio_min"] = by_key["ratio_min"].min()
