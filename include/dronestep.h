@@ -32,6 +32,10 @@
  *                             295-356, Actor_Critic_inference.ipynb:229-295, :444-500
  *                                          -> dd_mlp_forward_sampled (one frame's action)
  *                                             dd_policy_rollout_sampled (the episode loop)
+ *   evaluate_policy's `rewards` (the calc_reward dicts) as plot_accumulated_rewards /
+ *   evaluate_policy_simple accumulate them per component
+ *                             Actor_Critic_PPO.ipynb:1469-1532, :1543-1609, :997-1101
+ *                                          -> dd_policy_evaluate_parts
  *
  * One call processes a batch of N independent drones stored as a
  * struct-of-arrays (SoA) in device memory.  The reference has no FFI of its
@@ -60,7 +64,8 @@ extern "C" {
 #endif
 
 #define DD_ABI_VERSION 13 /* 13: DDSampling, DDEpisodeStats, dd_mlp_forward_sampled, dd_policy_rollout_sampled (additions only: the
-                              spawn stream and every existing entry point are ABI 12's); 12: spawns drawn from Philox4x32-7; 11: shaped_mode (REINFORCE reward), DDRolloutIO.kernel, dd_rollout_kernel,
+                              spawn stream and every existing entry point are ABI 12's; DDRewardParts and
+                              dd_policy_evaluate_parts were added to 13 the same way); 12: spawns drawn from Philox4x32-7; 11: shaped_mode (REINFORCE reward), DDRolloutIO.kernel, dd_rollout_kernel,
                               dd_device_errors; 10: DDStepIO.state_out (ping-pong state) */
 
 /* Storage precision of the SoA floating-point fields. */
@@ -518,6 +523,65 @@ int dd_policy_rollout_sampled(const DDConfig *cfg, const DDState *st, const floa
                               int32_t compute, const DDPolicyRolloutIO *io,
                               const DDSampling *sampling, const DDEpisodeStats *stats,
                               int64_t n, void *stream);
+
+/* ---- evaluate_policy with the reward's components ---------------------------
+ * calc_reward returns a dict; the notebooks' evaluate_policy keeps the list of
+ * them (`rewards`) and plot_accumulated_rewards / evaluate_policy_simple draw
+ * the running sum of every key.  dd_policy_evaluate_parts is the evaluation
+ * loop of dd_policy_rollout_sampled (sticky done, DDSampling, DDEpisodeStats)
+ * keeping the frame's DD_REWARD_PARTS = 8 values, in the notebooks' key order:
+ *   slot  Actor_Critic_PPO / _Basic (DD_SHAPED_PPO)   Policy_Gradients (DD_SHAPED_REINFORCE)
+ *   0     time_penalty                                time_penalty
+ *   1     distance                                    distance
+ *   2     hovering                                    velocity_alignment
+ *   3     angle                                       angle
+ *   4     speed                                       speed
+ *   5     vertical_position                           vertical_position
+ *   6     terminal                                    terminal
+ *   7     total                                       total
+ * total is summed in the notebook's order from the same doubles as the slots.
+ * The PPO notebook's quirk is kept: its time_penalty entry is
+ * -inverse_quadratic(dist, decay=100, scaler=1), but its total adds the literal
+ * -0.5 instead, so there slot 0 is reported and is NOT a term of slot 7
+ * (slot 7 = -0.5 + slots 1..6).  REINFORCE's slot 7 = slots 0..6, and equals
+ * the reward dd_step / dd_policy_rollout_sampled store, bit for bit.
+ * Rounding: a frame's eight values are the doubles rounded to the state's
+ * storage width (float / double by precision), as the stored reward is; the
+ * sums are double, added in frame order under DDEpisodeStats' rule (while
+ * ep_status[i] & DD_ST_DONE is clear at the start of the frame, the frame that
+ * ends the episode included).  Frames after a lane's episode has ended add
+ * nothing, and per_frame holds zeros for them.
+ * prev_state (PPO shape): the notebooks' evaluation passes the state the actor
+ * saw, ONE frame back; prev_dist[i] is that state's distance_to_platform as a
+ * double (of the unrounded frame).  The caller sets it before frame 0 to the
+ * reset state's value (dd_shaped_reset's slot 0; never NaN: prev_state is
+ * present from frame 0 on) and the call carries it forward, so the results do
+ * not depend on how the frames are split into launches.  The collection
+ * loop's two-frame history io->shaped_hist only selects the PPO shape, as in
+ * dd_policy_rollout_sampled: it is neither read nor written. */
+#define DD_REWARD_PARTS 8
+typedef struct DDRewardParts {
+    double *sum;       /* [8][N] in/out: per-episode sums, slot-major (required) */
+    double *prev_dist; /* [N] in/out; required for the PPO shape, unused otherwise */
+    void *per_frame;   /* [frames][8][N] float / double by precision, or NULL    */
+} DDRewardParts;
+
+/* io->obs0, obs_final, obs, actions, log_prob, reward, done, seed, step and
+ * frames as dd_policy_rollout_sampled (all per-frame buffers nullable);
+ * reward[k] is slot 7 of frame k.  io->max_steps is not read: the notebooks'
+ * evaluation stops after its frames without the collection loops' timeout
+ * penalty.  hipErrorInvalidValue, before any launch: every argument error of
+ * dd_policy_rollout_sampled (sampling mode, temperature, compute, packed
+ * alignment, n < 0, frames < 0); a NULL parts or parts->sum; the PPO shape with
+ * a NULL prev_dist; the engine's reward (DD_SHAPED_PPO with a NULL shaped_hist:
+ * it has no notebook components); io->engine_reward / engine_done set (not
+ * written here); cfg->auto_reset (one episode per lane); stats NULL or with
+ * fewer than its four pointers.  n == 0 is success; so is frames == 0, which
+ * writes obs_final if set and leaves every accumulator as it was. */
+int dd_policy_evaluate_parts(const DDConfig *cfg, const DDState *st, const float *packed,
+                             int32_t compute, const DDPolicyRolloutIO *io,
+                             const DDSampling *sampling, const DDEpisodeStats *stats,
+                             const DDRewardParts *parts, int64_t n, void *stream);
 
 /* ---- Rendering -------------------------------------
  * DroneGame.render() in 'rgb_array' mode (game_engine.py:300-337): the scene

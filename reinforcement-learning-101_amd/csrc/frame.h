@@ -1,8 +1,8 @@
 // frame.h — one drone's frame of DroneGame.step in IEEE double: world
 // constants, the lane state, Drone.apply_thrust / update, the reward cascade,
 // get_state's observation row and the notebooks' calc_reward.  Shared by the
-// step / rollout kernels (step.hip, rollout.hip) and the fused policy rollout
-// (policy_rollout.hip), so every path evaluates the same frame bit for bit.
+// step / rollout kernels (step.hip, rollout.hip) and the fused policy loops
+// (policy_rollout.hip, policy_eval.hip), so every path evaluates the same frame bit for bit.
 // The SoA plumbing around it (typed state pointers, lane loads and stores) is
 // lane_io.h's.  Compiled with -ffp-contract=off (see rollout.hip).
 #pragma once
@@ -769,6 +769,77 @@ __device__ __forceinline__ double reinforce_reward(const double v[13], uint32_t 
     const double crash_term = dist > 0.3 ? -200.0 - 100.0 : -200.0;
     total += landed ? 500.0 + fuel * 100.0 : crashed ? crash_term : 0.0;
     return total;
+}
+
+// The component forms: calc_reward's whole dict instead of its 'total', for the
+// evaluation that keeps the components (policy_eval.hip).  parts[] holds the
+// notebooks' keys in their order (DD_REWARD_PARTS, dronestep.h):
+//   0 time_penalty  1 distance  2 hovering (PPO) / velocity_alignment (REINFORCE)
+//   3 angle  4 speed  5 vertical_position  6 terminal  7 total
+// Every term is formed as notebook_reward / reinforce_reward form it, and the
+// total is summed from the same doubles in the same order, so parts[7] is
+// their return value bit for bit.  Branch-free (see frame()).
+//
+// The PPO notebook's quirk is kept: rewards['time_penalty'] is
+// -inverse_quadratic(dist, decay=100, scaler=1), but the total adds the literal
+// -0.5 in its place (Actor_Critic_PPO.ipynb:175-184), so slot 0 is reported
+// and is not a term of slot 7.
+__device__ __forceinline__ void notebook_reward_parts(const double v[13], uint32_t status, double prev_dist,
+                                                      double parts[8]) {
+    const double vx = v[2], vy = v[3], angle = v[4], fuel = v[6], dist = v[9], dx = v[10], dy = v[11],
+                 speed = v[12];
+    parts[0] = -(1.0 * (1.0 / (1.0 + (100.0 * (dist * dist))))) - 0.0;
+    const bool have_prev = !__builtin_isnan(prev_dist);
+    const double delta = prev_dist - dist;
+    const double vtp = dist > 1e-6 ? (vx * dx + vy * dy) / dist : 0.0;  // velocity toward platform
+    const bool fast_toward = (speed >= 0.15) & (vtp > 0.1) & (dist > 0.065);
+    const double clipped = fmin(fmax(delta * 1000 * (1.0 + speed * 2.0), -2.0), 5.0);  // np.clip
+    const bool away = !fast_toward & (delta < -0.001);
+    double distance = fast_toward ? clipped : away ? -2.0 * fabs(delta) * 1000 : 0.0;
+    double hovering = (fast_toward | away) ? 0.0 : speed < 0.05 ? -1.0 : speed < 0.15 ? -0.3 : 0.0;
+    parts[1] = have_prev ? distance : 0.0;
+    parts[2] = have_prev ? hovering : 0.0;
+    const double excess = fabs(angle) - (((0.20 - 0.111) * dist) + 0.111);
+    parts[3] = -(excess > 0.0 ? excess : 0.0);
+    const double over = dist < 1 ? speed - 0.1 : speed - 0.6;
+    parts[4] = (dist < 1 ? -2.0 : -1.0) * (over > 0.0 ? over : 0.0);
+    parts[5] = dy > 0.0 ? 0.0 : dy * 4.0;
+    const bool landed = status & DD_ST_LANDED, crashed = status & DD_ST_CRASHED;
+    const double crash_term = dist > 0.3 ? -200.0 - 100.0 : -200.0;
+    parts[6] = landed ? 800.0 + fuel * 100.0 : crashed ? crash_term : 0.0;
+    double total = 0.0;
+    total += -0.5;  // (not parts[0]: the notebook's own line)
+#pragma unroll
+    for (int j = 1; j < 7; ++j) total += parts[j];
+    parts[7] = total;
+}
+
+__device__ __forceinline__ void reinforce_reward_parts(const double v[13], uint32_t status, double parts[8]) {
+    const double vx = v[2], vy = v[3], angle = v[4], fuel = v[6], dist = v[9], dx = v[10], dy = v[11],
+                 speed = v[12];
+    constexpr double kScale = 1.0 - 0.3;  // as reinforce_reward
+    parts[0] = -(kScale * (1.0 / (1.0 + (50.0 * (dist * dist))))) - 0.3;
+    const double odx0 = -dx, ody0 = -dy;
+    const double onorm = sqrt(odx0 * odx0 + ody0 * ody0);
+    const double odx = odx0 / onorm, ody = ody0 / onorm;
+    const double align_v = (vx / speed) * odx + (vy / speed) * ody;
+    const double align = onorm < 1e-6 ? 1.0 : speed < 1e-6 ? 0.0 : align_v;
+    const bool above = (dist > 0.065) & (dy > 0.0);
+    const double sig = 4.5 * (1.0 / (1.0 + exp(10.0 * (dist - 0.5))));  // scaled_shifted_negative_sigmoid
+    parts[1] = above ? ((align > 0.0 ? 1.0 : 0.0) * speed) * sig : 0.0;
+    parts[2] = (above & (align > 0.0)) ? 0.5 : 0.0;
+    const double excess = fabs(angle) - (((0.20 - 0.111) * dist) + 0.111);
+    parts[3] = -(excess > 0.0 ? excess : 0.0);
+    const double over = dist < 1 ? speed - 0.1 : speed - 0.4;
+    parts[4] = (dist < 1 ? -2.0 : -1.0) * (over > 0.0 ? over : 0.0);
+    parts[5] = dy > 0.0 ? 0.0 : dy * 4.0;
+    const bool landed = status & DD_ST_LANDED, crashed = status & DD_ST_CRASHED;
+    const double crash_term = dist > 0.3 ? -200.0 - 100.0 : -200.0;
+    parts[6] = landed ? 500.0 + fuel * 100.0 : crashed ? crash_term : 0.0;
+    double total = parts[0];
+#pragma unroll
+    for (int j = 1; j < 7; ++j) total += parts[j];
+    parts[7] = total;
 }
 
 // The state between two frames is what dd_step would store: rounded to the

@@ -8,7 +8,9 @@ surface (:class:`VecDroneEnv`) and the reference's per-game APIs
 policy / value networks (:class:`MlpNet`, f32 MFMA) and GAE (:func:`gae`)
 for on-device collection, and the notebooks' ``evaluate_policy`` (temperature
 or greedy action selection, one episode per lane:
-:meth:`VecDroneEnv.evaluate_policy`); and the notebooks' training batches
+:meth:`VecDroneEnv.evaluate_policy`, with ``calc_reward``'s components kept
+per lane and per frame on request: :func:`notebook_rewards`); and the
+notebooks' training batches
 built from rollout buffers on device (:func:`ppo_batch`,
 :func:`reinforce_batch`, :func:`collect_ppo`), from each lane's first
 episode or from every episode of an auto-reset rollout
@@ -40,6 +42,7 @@ from .shuffle import ShuffledBatch, shuffle_batch, shuffle_indices
 from .adamw import AdamW, PpoUpdate, ppo_update
 from .pg_loss import ReinforceLosses, ReinforceUpdate, collect_reinforce, reinforce_losses, reinforce_update
 from .pg_loss import ActorCriticUpdate, TdLosses, actor_critic_update, td_losses
+from .reward_parts import notebook_rewards
 
 __all__ = [
     "EnvConfig", "VecDroneEnv", "StepInfo", "OBS_KEYS",
@@ -52,5 +55,6 @@ __all__ = [
     "shuffle_batch", "shuffle_indices", "ShuffledBatch",
     "reinforce_losses", "ReinforceLosses", "reinforce_update", "ReinforceUpdate", "collect_reinforce",
     "td_losses", "TdLosses", "actor_critic_update", "ActorCriticUpdate",
+    "notebook_rewards",
 ]
 __version__ = "0.1.0"

@@ -27,7 +27,7 @@ __all__ = [
     "DD_ADAMW_REFUSED", "DDAdamWHyper", "DDAdamWState", "DDAdamWIO",
     "DD_PG_LOSS", "DD_PG_COUNT", "DD_PG_RESULTS", "DDPgLossIO",
     "DD_TD_CRITIC_LOSS", "DD_TD_MSE", "DD_TD_VALUE_REG", "DD_TD_COUNT", "DD_TD_RESULTS", "DDTdLossIO",
-    "DDShuffleIO",
+    "DDShuffleIO", "DD_REWARD_PARTS", "DDRewardParts", "REWARD_PART_NAMES",
     "sampling_mode", "lib", "load", "library_path", "check",
     "NativeLibraryError",
 ]
@@ -46,6 +46,14 @@ DD_ERR_HANDOVER = 1
 DD_MEM_DEFAULT, DD_MEM_CONTIGUOUS = 0, 1
 DD_SAMPLE_BERNOULLI, DD_SAMPLE_TEMPERED, DD_SAMPLE_GREEDY = 0, 1, 2
 DD_BATCH_GAE, DD_BATCH_RETURNS = 0, 1
+DD_REWARD_PARTS = 8
+#: calc_reward's keys in the notebooks' order, by ``reward_mode`` (the slots of ``DDRewardParts``)
+REWARD_PART_NAMES = {
+    "notebook": ("time_penalty", "distance", "hovering", "angle", "speed", "vertical_position", "terminal",
+                 "total"),
+    "reinforce": ("time_penalty", "distance", "velocity_alignment", "angle", "speed", "vertical_position",
+                  "terminal", "total"),
+}
 DD_EPISODES_DROP_OPEN = 1
 (DD_PPO_TOTAL_LOSS, DD_PPO_POLICY_LOSS, DD_PPO_VALUE_LOSS, DD_PPO_ENTROPY, DD_PPO_RATIO_MEAN, DD_PPO_RATIO_MIN,
  DD_PPO_RATIO_MAX, DD_PPO_RATIO_STD, DD_PPO_CLIPPED_FRAC, DD_PPO_RESULTS) = range(10)
@@ -151,6 +159,10 @@ class DDSampling(ctypes.Structure):
 class DDEpisodeStats(ctypes.Structure):
     _fields_ = [("ep_return", ctypes.c_void_p), ("ep_steps", ctypes.c_void_p), ("ep_status", ctypes.c_void_p),
                 ("ep_fuel", ctypes.c_void_p)]
+
+
+class DDRewardParts(ctypes.Structure):
+    _fields_ = [("sum", ctypes.c_void_p), ("prev_dist", ctypes.c_void_p), ("per_frame", ctypes.c_void_p)]
 
 
 class DDBatchLayout(ctypes.Structure):
@@ -288,6 +300,10 @@ EXPORTS = {
     "dd_policy_rollout_sampled": (ctypes.c_int, [ctypes.POINTER(DDConfig), ctypes.POINTER(DDState), ctypes.c_void_p,
                                                  _I, ctypes.POINTER(DDPolicyRolloutIO), ctypes.POINTER(DDSampling),
                                                  ctypes.POINTER(DDEpisodeStats), ctypes.c_int64, ctypes.c_void_p]),
+    "dd_policy_evaluate_parts": (ctypes.c_int, [ctypes.POINTER(DDConfig), ctypes.POINTER(DDState), ctypes.c_void_p,
+                                                _I, ctypes.POINTER(DDPolicyRolloutIO), ctypes.POINTER(DDSampling),
+                                                ctypes.POINTER(DDEpisodeStats), ctypes.POINTER(DDRewardParts),
+                                                ctypes.c_int64, ctypes.c_void_p]),
     "dd_render": (ctypes.c_int, [ctypes.POINTER(DDConfig), ctypes.POINTER(DDState), ctypes.c_void_p,
                                  ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_void_p, _I,
                                  ctypes.c_void_p]),
@@ -350,7 +366,8 @@ _LAB_OPTIONAL = ("dd_build_info", "dd_selftest_sqrt", "dd_rollout_kernel", "dd_d
                  "dd_episodes_fill", "dd_episodes_gather", "dd_episodes_advantages", "dd_mlp_evaluate_actions",
                  "dd_ppo_loss_workspace", "dd_ppo_losses", "dd_mlp_backward_workspace", "dd_mlp_backward",
                  "dd_adamw_state_bytes", "dd_adamw_init", "dd_adamw_step", "dd_pg_loss_workspace", "dd_pg_losses",
-                 "dd_td_loss_workspace", "dd_td_losses", "dd_shuffle_indices", "dd_shuffle_rows")
+                 "dd_td_loss_workspace", "dd_td_losses", "dd_shuffle_indices", "dd_shuffle_rows",
+                 "dd_policy_evaluate_parts")
 
 
 class NativeLibraryError(RuntimeError):
