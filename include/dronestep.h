@@ -36,6 +36,8 @@
  *   evaluate_policy_simple accumulate them per component
  *                             Actor_Critic_PPO.ipynb:1469-1532, :1543-1609, :997-1101
  *                                          -> dd_policy_evaluate_parts
+ *   run_inference_loop's table for several checkpoints (one policy per group of lanes)
+ *                             Actor_Critic_inference.ipynb:229-295   -> dd_policy_rollout_population
  *
  * One call processes a batch of N independent drones stored as a
  * struct-of-arrays (SoA) in device memory.  The reference has no FFI of its
@@ -65,7 +67,7 @@ extern "C" {
 
 #define DD_ABI_VERSION 13 /* 13: DDSampling, DDEpisodeStats, dd_mlp_forward_sampled, dd_policy_rollout_sampled (additions only: the
                               spawn stream and every existing entry point are ABI 12's; DDRewardParts and
-                              dd_policy_evaluate_parts were added to 13 the same way); 12: spawns drawn from Philox4x32-7; 11: shaped_mode (REINFORCE reward), DDRolloutIO.kernel, dd_rollout_kernel,
+                              dd_policy_evaluate_parts, then dd_policy_rollout_population, were added to 13 the same way); 12: spawns drawn from Philox4x32-7; 11: shaped_mode (REINFORCE reward), DDRolloutIO.kernel, dd_rollout_kernel,
                               dd_device_errors; 10: DDStepIO.state_out (ping-pong state) */
 
 /* Storage precision of the SoA floating-point fields. */
@@ -523,6 +525,34 @@ int dd_policy_rollout_sampled(const DDConfig *cfg, const DDState *st, const floa
                               int32_t compute, const DDPolicyRolloutIO *io,
                               const DDSampling *sampling, const DDEpisodeStats *stats,
                               int64_t n, void *stream);
+
+/* ---- A population of actors in one launch -----------------------------------
+ * dd_policy_rollout_sampled with the lanes [0, n) split into `members`
+ * contiguous groups of lanes_per_member = L lanes, group g driven by the packed
+ * image packed_table[g] (dd_mlp_pack, out_dim 3, all of `compute`): checkpoint
+ * tournaments and sweeps fill the card with one launch where P launches of L
+ * lanes each leave most of it idle.  Equal, bit for bit, to `members` calls of
+ * dd_policy_rollout_sampled on the sub-batches [g L, (g+1) L), each with
+ * env_id_base + g L and packed_table[g], writing the matching lane columns of
+ * the same [frames][n] buffers, shaped_hist [2][n] and DDEpisodeStats [n]
+ * (Philox is keyed by env id, so a lane's draws do not depend on its group's
+ * neighbours).  members == 1 is dd_policy_rollout_sampled exactly.
+ * packed_table is DEVICE memory, [members] pointers to device images, each
+ * 16-byte aligned, and is read by the kernel: the call copies no weight and
+ * no pointer, so a member re-packed in place (same address) is seen by the next
+ * launch on the stream, and the table must stay valid until the launch is done.
+ * A block of 256 lanes belongs to one group (the grid is members *
+ * ceil(L / 256) blocks); an image of the wrong layout gives NaN by its tag, as
+ * in dd_mlp_forward.
+ * hipErrorInvalidValue, before any launch: every argument error of
+ * dd_policy_rollout_sampled; a NULL or not 8-byte-aligned packed_table;
+ * members < 1; lanes_per_member < 1; members * lanes_per_member != n for
+ * n > 0.  n == 0 and frames == 0 behave as in dd_policy_rollout_sampled. */
+int dd_policy_rollout_population(const DDConfig *cfg, const DDState *st,
+                                 const float *const *packed_table, int32_t members,
+                                 int64_t lanes_per_member, int32_t compute,
+                                 const DDPolicyRolloutIO *io, const DDSampling *sampling,
+                                 const DDEpisodeStats *stats, int64_t n, void *stream);
 
 /* ---- evaluate_policy with the reward's components ---------------------------
  * calc_reward returns a dict; the notebooks' evaluate_policy keeps the list of

@@ -87,24 +87,54 @@ struct EvalArgs : Args {
     void* ep_fuel;
 };
 
+// dd_policy_rollout_population's launch: the lanes [0, n) are `members` groups
+// of lanes_per_member lanes, group g driven by packed_table[g].  A block
+// belongs to one group (blocks_per_member blocks each) and loads that group's
+// image; its tiles end at the group's end.  Everything indexed by lane keeps
+// its global index.  Again a type of its own, so the kernels above stay the
+// instantiations they were.
+struct PopArgs : EvalArgs {
+    const float* const* packed_table;  // device, [members]
+    int64_t lanes_per_member;
+    int32_t members;
+    int32_t blocks_per_member;         // ceil(lanes_per_member / (kWaves * kCols))
+};
+
+// A wave's first lane, and the end of the lanes its block's network drives: one batch ...
+__device__ __forceinline__ int64_t first_lane(const Args& p, int wave) {
+    return ((int64_t)blockIdx.x * kWaves + wave) * kCols;
+}
+__device__ __forceinline__ int64_t lanes_end(const Args& p) { return p.n; }
+// ... or group g = block / blocks_per_member, whose tiles count from its lane g * L
+__device__ __forceinline__ int64_t first_lane(const PopArgs& p, int wave) {
+    const unsigned g = blockIdx.x / (unsigned)p.blocks_per_member;
+    return (int64_t)g * p.lanes_per_member +
+           ((int64_t)(blockIdx.x % (unsigned)p.blocks_per_member) * kWaves + wave) * kCols;
+}
+__device__ __forceinline__ int64_t lanes_end(const PopArgs& p) {
+    return (int64_t)(blockIdx.x / (unsigned)p.blocks_per_member + 1) * p.lanes_per_member;
+}
+
 template <typename T, bool kSplit, bool kRef, typename P>
 __global__ __launch_bounds__(kThreads) void policy_rollout_kernel(const float* __restrict__ packed, P p,
                                                                   Soa<T> a) {
-    constexpr bool kEval = std::is_same<P, EvalArgs>::value;
+    constexpr bool kEval = std::is_base_of<EvalArgs, P>::value;
+    constexpr bool kPop = std::is_same<P, PopArgs>::value;
     extern __shared__ f32x4 lds4[];
     float* lds = reinterpret_cast<float*>(lds4);
+    if constexpr (kPop) packed = p.packed_table[blockIdx.x / (unsigned)p.blocks_per_member];  // the group's image
     for (int i = threadIdx.x; i < kPacked / 4; i += kThreads)
         lds4[i] = mlp::packed_fragment(reinterpret_cast<const f32x4*>(packed), i,
                                        mlp::pack_tag(kSplit ? DD_MLP_F16X3 : DD_MLP_F32, 3));
     __syncthreads();  // the only block barrier: waves run their frames independently
 
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, h = lane >> 5, c = lane & 31;
-    const int64_t d0 = ((int64_t)blockIdx.x * kWaves + wave) * kCols;
-    if (d0 >= p.n) return;
-    const int rows = (int)min((int64_t)kCols, p.n - d0);
+    const int64_t d0 = first_lane(p, wave);
+    if (d0 >= lanes_end(p)) return;
+    const int rows = (int)min((int64_t)kCols, lanes_end(p) - d0);
     const bool live = c < rows;
     const bool writer = live && h == 0;  // one lane per drone stores its per-frame outputs
-    const int64_t d = live ? d0 + c : p.n - 1;  // lanes past n shadow the last drone
+    const int64_t d = live ? d0 + c : lanes_end(p) - 1;  // lanes past the end shadow the last drone (of the group)
     float* slice = lds + kPacked + wave * kRowFloats;
     const DDConfig& sw = p.k.c;
     const Consts& k = kRef ? kRefConsts : p.k;
@@ -274,7 +304,8 @@ hipError_t launch(const float* packed, const P& p, const Soa<T>& a, hipStream_t 
                                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsBytes);
     if (e != hipSuccess) return e;
     const int64_t tiles = (p.n + kCols - 1) / kCols;
-    const unsigned blocks = (unsigned)((tiles + kWaves - 1) / kWaves);  // one wave per 32-drone tile
+    unsigned blocks = (unsigned)((tiles + kWaves - 1) / kWaves);  // one wave per 32-drone tile
+    if constexpr (std::is_same<P, PopArgs>::value) blocks = (unsigned)p.members * (unsigned)p.blocks_per_member;
     hipLaunchKernelGGL((policy_rollout_kernel<T, kSplit, kRef, P>), dim3(blocks), dim3(kThreads), kLdsBytes, s,
                        packed, p, a);
     return hipGetLastError();
@@ -303,10 +334,23 @@ extern "C" int dd_policy_rollout(const DDConfig* cfg, const DDState* st, const f
     return dd_policy_rollout_sampled(cfg, st, packed, compute, io, nullptr, nullptr, n, stream);
 }
 
-extern "C" int dd_policy_rollout_sampled(const DDConfig* cfg, const DDState* st, const float* packed,
-                                         int32_t compute, const DDPolicyRolloutIO* io, const DDSampling* sampling,
-                                         const DDEpisodeStats* stats, int64_t n, void* stream) {
+// dd_policy_rollout_sampled (table == nullptr: one network, `packed`) and
+// dd_policy_rollout_population (table: the groups' images; `packed` unused).
+static int rollout_checked(const DDConfig* cfg, const DDState* st, const float* packed,
+                           const float* const* table, int32_t members, int64_t lanes_per_member, int32_t compute,
+                           const DDPolicyRolloutIO* io, const DDSampling* sampling, const DDEpisodeStats* stats,
+                           int64_t n, void* stream) {
     if (!cfg || !io || !dd::state_ok(st) || n < 0 || io->frames < 0) return hipErrorInvalidValue;
+    int64_t blocks_per_member = 0;
+    if (table) {  // the groups tile [0, n) exactly; the grid is members * blocks_per_member blocks
+        if ((reinterpret_cast<uintptr_t>(table) & 7u) || members < 1 || lanes_per_member < 1)
+            return hipErrorInvalidValue;
+        // members * lanes_per_member == n, without the product
+        if (n > 0 && (n % lanes_per_member != 0 || n / lanes_per_member != members)) return hipErrorInvalidValue;
+        constexpr int64_t kBlockLanes = dd::prl::kWaves * dd::prl::kCols;
+        blocks_per_member = lanes_per_member / kBlockLanes + (lanes_per_member % kBlockLanes != 0);
+        if (n > 0 && blocks_per_member * members > INT32_MAX) return hipErrorInvalidValue;
+    }
     if (sampling) {
         if (sampling->mode != DD_SAMPLE_BERNOULLI && sampling->mode != DD_SAMPLE_TEMPERED &&
             sampling->mode != DD_SAMPLE_GREEDY)
@@ -326,7 +370,7 @@ extern "C" int dd_policy_rollout_sampled(const DDConfig* cfg, const DDState* st,
     if (shape < 0) return hipErrorInvalidValue;
     if (n == 0) return hipSuccess;
     // the per-frame buffers are optional only next to the statistics
-    if (!packed || !io->obs0 || (io->frames > 0 && !with_stats && (!io->reward || !io->done)))
+    if ((!table && !packed) || !io->obs0 || (io->frames > 0 && !with_stats && (!io->reward || !io->done)))
         return hipErrorInvalidValue;
     if (reinterpret_cast<uintptr_t>(packed) & 15u) return hipErrorInvalidValue;  // read as 16-byte fragments
     if (io->frames == 0 && io->obs_final == nullptr) return hipSuccess;
@@ -354,8 +398,15 @@ extern "C" int dd_policy_rollout_sampled(const DDConfig* cfg, const DDState* st,
     const hipStream_t s = (hipStream_t)stream;
     // the plain Bernoulli draw with no probs_used and no statistics is the collection kernel
     const bool eval = with_stats || (sampling && (sampling->mode != DD_SAMPLE_BERNOULLI || sampling->probs_used));
-    if (!eval) return (int)dd::prl::launch_for(*st, compute, ref, packed, p, s);
-    dd::prl::EvalArgs q{};
+    if (!eval && !table) return (int)dd::prl::launch_for(*st, compute, ref, packed, p, s);
+    if (table) {
+        // A tile starts at lane g * L + 32 k: its rows are 16-byte aligned only if L % 4 == 0 (then n % 4 == 0
+        // too).  One group starts at lane 0, as dd_policy_rollout_sampled's tiles do.
+        const bool lanes4 = (lanes_per_member & 3) == 0;
+        p.rows_aligned = p.rows_aligned && lanes4;
+        p.final_aligned = p.final_aligned && (lanes4 || members == 1);
+    }
+    dd::prl::PopArgs q{};
     static_cast<dd::prl::Args&>(q) = p;
     q.mode = sampling ? sampling->mode : DD_SAMPLE_BERNOULLI;
     q.temperature = sampling ? sampling->temperature : 1.0f;
@@ -366,5 +417,25 @@ extern "C" int dd_policy_rollout_sampled(const DDConfig* cfg, const DDState* st,
         q.ep_status = stats->ep_status;
         q.ep_fuel = stats->ep_fuel;
     }
-    return (int)dd::prl::launch_for(*st, compute, ref, packed, q, s);
+    if (!table) return (int)dd::prl::launch_for<dd::prl::EvalArgs>(*st, compute, ref, packed, q, s);
+    q.packed_table = table;
+    q.lanes_per_member = lanes_per_member;
+    q.members = members;
+    q.blocks_per_member = (int32_t)blocks_per_member;
+    return (int)dd::prl::launch_for(*st, compute, ref, nullptr, q, s);
+}
+
+extern "C" int dd_policy_rollout_sampled(const DDConfig* cfg, const DDState* st, const float* packed,
+                                         int32_t compute, const DDPolicyRolloutIO* io, const DDSampling* sampling,
+                                         const DDEpisodeStats* stats, int64_t n, void* stream) {
+    return rollout_checked(cfg, st, packed, nullptr, 1, n, compute, io, sampling, stats, n, stream);
+}
+
+extern "C" int dd_policy_rollout_population(const DDConfig* cfg, const DDState* st, const float* const* packed_table,
+                                            int32_t members, int64_t lanes_per_member, int32_t compute,
+                                            const DDPolicyRolloutIO* io, const DDSampling* sampling,
+                                            const DDEpisodeStats* stats, int64_t n, void* stream) {
+    if (!packed_table) return hipErrorInvalidValue;
+    return rollout_checked(cfg, st, nullptr, packed_table, members, lanes_per_member, compute, io, sampling, stats, n,
+                           stream);
 }

@@ -26,14 +26,16 @@ epoch loop on device (:class:`AdamW`, :func:`ppo_update`,
 on device); and the other two training notebooks'
 learners: REINFORCE (:func:`collect_reinforce`, :func:`reinforce_losses`,
 :func:`reinforce_update`) and the one-step TD actor-critic
-(:func:`td_losses`, :func:`actor_critic_update`).
+(:func:`td_losses`, :func:`actor_critic_update`); and several actors in one
+fused launch, each on its own group of lanes (:class:`ActorPopulation`,
+:func:`population_summary`: a checkpoint tournament or a sweep's collection).
 """
 from .config import EnvConfig
 from .vec_env import OBS_KEYS, StepInfo, VecDroneEnv
 from .compat import DroneGame, DroneGameClient, DroneState, action_bits
 from .sharding import dist_env, gather_obs, shard_bounds
 from .gae import gae
-from .policy import MlpNet
+from .policy import ActorPopulation, MlpNet, population_summary
 from .train_batch import collect_ppo, ppo_batch, reinforce_batch
 from .train_batch import collect_ppo_steps, ppo_episodes_batch, reinforce_episodes_batch
 from .ppo_loss import PpoLosses, ppo_losses
@@ -55,6 +57,6 @@ __all__ = [
     "shuffle_batch", "shuffle_indices", "ShuffledBatch",
     "reinforce_losses", "ReinforceLosses", "reinforce_update", "ReinforceUpdate", "collect_reinforce",
     "td_losses", "TdLosses", "actor_critic_update", "ActorCriticUpdate",
-    "notebook_rewards",
+    "notebook_rewards", "ActorPopulation", "population_summary",
 ]
 __version__ = "0.1.0"

@@ -304,6 +304,10 @@ EXPORTS = {
                                                 _I, ctypes.POINTER(DDPolicyRolloutIO), ctypes.POINTER(DDSampling),
                                                 ctypes.POINTER(DDEpisodeStats), ctypes.POINTER(DDRewardParts),
                                                 ctypes.c_int64, ctypes.c_void_p]),
+    "dd_policy_rollout_population": (ctypes.c_int, [ctypes.POINTER(DDConfig), ctypes.POINTER(DDState),
+                                                    ctypes.c_void_p, _I, ctypes.c_int64, _I,
+                                                    ctypes.POINTER(DDPolicyRolloutIO), ctypes.POINTER(DDSampling),
+                                                    ctypes.POINTER(DDEpisodeStats), ctypes.c_int64, ctypes.c_void_p]),
     "dd_render": (ctypes.c_int, [ctypes.POINTER(DDConfig), ctypes.POINTER(DDState), ctypes.c_void_p,
                                  ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_void_p, _I,
                                  ctypes.c_void_p]),
@@ -367,7 +371,7 @@ _LAB_OPTIONAL = ("dd_build_info", "dd_selftest_sqrt", "dd_rollout_kernel", "dd_d
                  "dd_ppo_loss_workspace", "dd_ppo_losses", "dd_mlp_backward_workspace", "dd_mlp_backward",
                  "dd_adamw_state_bytes", "dd_adamw_init", "dd_adamw_step", "dd_pg_loss_workspace", "dd_pg_losses",
                  "dd_td_loss_workspace", "dd_td_losses", "dd_shuffle_indices", "dd_shuffle_rows",
-                 "dd_policy_evaluate_parts")
+                 "dd_policy_evaluate_parts", "dd_policy_rollout_population")
 
 
 class NativeLibraryError(RuntimeError):

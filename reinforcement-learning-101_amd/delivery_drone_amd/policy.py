@@ -26,13 +26,14 @@ from __future__ import annotations
 
 import ctypes
 import math
+from collections.abc import Sequence
 from typing import Dict, Mapping, Optional, Tuple
 
 import torch
 
 from . import abi
 
-__all__ = ["MlpNet", "STATE_DICT_KEYS"]
+__all__ = ["MlpNet", "STATE_DICT_KEYS", "ActorPopulation", "population_summary"]
 
 #: state_dict keys of the notebooks' nn.Sequential (``network.<i>.<param>``)
 STATE_DICT_KEYS = ("0.weight", "0.bias", "1.weight", "1.bias", "3.weight", "3.bias", "4.weight", "4.bias",
@@ -346,3 +347,86 @@ class MlpNet:
         abi.check(self._lib.dd_mlp_backward(ctypes.byref(p), ctypes.byref(io), m, ws.data_ptr(), self._stream()),
                   "dd_mlp_backward")
         return grads, norm
+
+
+class ActorPopulation(Sequence):
+    """Several actors that share one fused rollout launch
+    (``dd_policy_rollout_population``): a checkpoint tournament, the snapshots
+    of a training run, the learners of a hyper-parameter sweep.
+
+    ``actors`` is a non-empty sequence of :class:`MlpNet` with ``out_dim ==
+    3``, all on one device, of one ``compute`` and one library; anything else
+    raises ``ValueError``.  Passed to :meth:`VecDroneEnv.policy_rollout` or
+    :meth:`VecDroneEnv.evaluate_policy` in an actor's place, member ``g``
+    drives the env's lanes ``lanes(env, g)``, the ``g``-th of ``len(self)``
+    equal contiguous groups, exactly as it would drive an env of those lanes
+    alone (same ``env_id_base + start``): Philox is keyed by env id, so the
+    results are the single-actor ones bit for bit.
+
+    The constructor builds the device table of the members'
+    ``packed.data_ptr()`` once and keeps the members alive.  A launch reads
+    the table and the images on the device and copies neither, and
+    ``MlpNet.packed`` keeps its address through :meth:`MlpNet.load_state_dict`
+    and :meth:`AdamW.step`: a member's new weights are seen by the next
+    population launch on the stream with nothing rebuilt.
+    """
+
+    def __init__(self, actors):
+        members = tuple(actors)
+        if not members:
+            raise ValueError("ActorPopulation needs at least one actor")
+        for a in members:
+            if not isinstance(a, MlpNet) or a.out_dim != 3:
+                raise ValueError("every member must be an actor: an MlpNet with out_dim 3")
+        first = members[0]
+        for a in members[1:]:
+            if a.device != first.device:
+                raise ValueError(f"the members are on different devices ({first.device}, {a.device})")
+            if a.compute != first.compute:
+                raise ValueError(f"the members differ in compute ({first.compute!r}, {a.compute!r}): "
+                                 "one launch runs one kernel")
+            if a._lib is not first._lib:
+                raise ValueError("the members use different builds of the library")
+        self._members = members
+        self.device, self.compute, self.out_dim = first.device, first.compute, 3
+        self._lib = first._lib
+        self.table = torch.tensor([a.packed.data_ptr() for a in members], dtype=torch.int64, device=self.device)
+
+    def __len__(self) -> int:
+        return len(self._members)
+
+    def __getitem__(self, g):
+        return self._members[g]
+
+    def lanes(self, env, g: int) -> slice:
+        """The lanes of ``env`` that member ``g`` drives."""
+        n, p = len(env), len(self._members)
+        if n % p != 0:
+            raise ValueError(f"{n} lanes do not split into {p} equal groups")
+        g = range(p)[g]
+        return slice(g * (n // p), (g + 1) * (n // p))
+
+
+def population_summary(result: Mapping[str, torch.Tensor], members: int) -> Dict[str, torch.Tensor]:
+    """``run_inference_loop``'s table (Actor_Critic_inference.ipynb:229-295)
+    for every member of a population: from the dict
+    :meth:`VecDroneEnv.evaluate_policy` returned for an
+    :class:`ActorPopulation` of ``members`` actors, the ``[members]`` float64
+    device tensors ``success_rate`` (the fraction of the member's lanes that
+    landed), ``mean_reward``, ``mean_steps`` and ``mean_final_fuel``.  Torch
+    reductions over the ``[members, L]`` views; nothing is read back.  Each
+    is the float64 sum over the member's lanes divided by ``L`` (a true
+    division, so the two integer columns, whose sums are exact, give the
+    correctly rounded mean)."""
+    members = int(members)
+    n = result["steps"].shape[0]
+    if members < 1 or n % members != 0:
+        raise ValueError(f"{n} lanes do not split into {members} equal groups")
+    # a tensor divisor: dividing by a Python number multiplies by its rounded reciprocal
+    lanes = torch.full((), n // members, dtype=torch.float64, device=result["steps"].device)
+
+    def mean(t):
+        return t.view(members, n // members).to(torch.float64).sum(dim=1) / lanes
+
+    return {"success_rate": mean(result["landed"]), "mean_reward": mean(result["total_reward"]),
+            "mean_steps": mean(result["steps"]), "mean_final_fuel": mean(result["final_fuel"])}
