@@ -22,6 +22,57 @@ LAYERS = (("0", "1"), ("3", "4"), ("6", "7"))
 U = 2.0 ** -24
 
 
+TINY = np.float32(2.0 ** -100)
+# "relu": (unit, gamma, beta) of every LayerNorm, n its width.  gamma = 0 makes
+# y = beta exactly in float32 and float64 alike, so [y > 0] is unambiguous.
+RELU_UNITS = ((3, 0.0, 0.0), (17, 0.0, TINY), (40, 0.0, -TINY), (-1, 0.0, 0.0), (0, 0.0, TINY))
+RELU_OFF, RELU_ON = (3, 40, -1), (17, 0)
+VARIANTS = ("relu", "var0")
+
+
+def crafted(sd, variant):
+    """A fixture network with the edges the fixture rows never reach, as a new
+    float32 state_dict (sd is left alone).
+    "relu": units 3, 40 and n - 1 of every LayerNorm have y = 0, -2^-100, 0 on
+    every row (no gradient passes), units 17 and 0 have y = 2^-100 (it passes
+    on every row).
+    "var0": 0.weight = 0 and 0.bias = 0.25: layer 1 has zero variance, xh = 0
+    exactly and rstd = 1 / sqrt(eps)."""
+    out = {k: np.array(sd[k], dtype=np.float32) for k in KEYS}
+    if variant == "relu":
+        for _, ln in LAYERS:
+            for j, gamma, beta in RELU_UNITS:
+                out[ln + ".weight"][j] = gamma
+                out[ln + ".bias"][j] = beta
+    elif variant == "var0":
+        out["0.weight"][:] = 0.0
+        out["0.bias"][:] = 0.25
+    else:
+        raise ValueError(variant)
+    return out
+
+
+def crafted_zeros(sd, variant):
+    """{name: (key, index)} of the gradient elements that are exact zeros on
+    the crafted network by construction, whatever the rows: dgamma and dbeta
+    of a unit that passes no gradient, and the next Linear's dW column of a
+    unit whose activation is 0 (and dgamma of a unit whose xh is 0)."""
+    nxt = {"1": "3.weight", "4": "6.weight", "7": "9.weight"}
+    zeros = {}
+    if variant == "relu":
+        for _, ln in LAYERS:
+            for j in RELU_OFF:
+                zeros[f"dgamma {ln}.weight[{j}]"] = (ln + ".weight", j)
+                zeros[f"dbeta {ln}.bias[{j}]"] = (ln + ".bias", j)
+                zeros[f"{nxt[ln]}[:, {j}]"] = (nxt[ln], (slice(None), j))
+    else:
+        zeros["dgamma 1.weight (xh = 0)"] = ("1.weight", slice(None))
+        for j in np.flatnonzero(np.asarray(sd["1.bias"]) <= 0):  # y = beta exactly
+            zeros[f"dbeta 1.bias[{j}]"] = ("1.bias", j)
+            zeros[f"3.weight[:, {j}]"] = ("3.weight", (slice(None), j))
+    return zeros
+
+
 def _f64(sd):
     return {k: np.asarray(sd[k], dtype=np.float64) for k in KEYS}
 

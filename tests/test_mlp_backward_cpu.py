@@ -113,6 +113,37 @@ def test_reference_gap(fx, restated):
         assert abs(float(fx[f"{tag}_norm"]) - restated[tag][2]) <= 1e-6 * restated[tag][2]
 
 
+@pytest.mark.parametrize("variant", ref.VARIANTS)
+@pytest.mark.parametrize("tag,key", NETS)
+def test_reference_gap_on_the_crafted_networks(g, nets, tag, key, variant):
+    """tests/test_gpu_mlp_backward_exact.py holds the kernel to 4 G 2^-24 S on
+    mlp_backward_ref.crafted's networks (the ReLU edge y = 0 and +-2^-100 with
+    gamma = 0; a layer of zero variance) with the fixture's G: fair only if
+    float32 autograd itself stays inside G there.  Measured: actor relu 5,887
+    (its 6.weight), var0 31; critic relu 229, var0 84; the fixture's G is
+    10,191.  gap_units asserts that where S = 0 autograd gives an exact zero:
+    dgamma, dbeta and the next Linear's column of every off unit."""
+    import torch
+    sd = ref.crafted(nets[tag], variant)
+    head = np.asarray(ppo_loss_ref.fixture_losses(g)[key]).astype(np.float32)
+    want, S, _ = ref.backward(sd, g["states"], head.astype(np.float64))
+    body = torch.nn.Sequential(*list(gd.torch_mlp(sd).children())[:10])  # up to the last Linear, float32
+    z = body(torch.from_numpy(g["states"]))
+    z.backward(torch.from_numpy(head.reshape(tuple(z.shape))))
+    got = {k: p.grad.numpy() for k, p in body.named_parameters()}
+    units = ref.gap_units(got, want, S)
+    worst = max(units, key=units.get)
+    print(f"crafted {tag} {variant}: gap {units[worst]:.0f} x 2^-24 S (its {worst})",
+          {k: round(v, 1) for k, v in units.items()})
+    assert units[worst] <= G_CAP
+    for name, (k, idx) in ref.crafted_zeros(sd, variant).items():
+        assert not np.any(S[k][idx]) and not np.any(want[k][idx]) and not np.any(got[k][idx]), name
+    if variant == "relu":  # the on units pass their gradient: a next-layer column of about 1e-32, normal
+        for ln, nxt in (("1", "3.weight"), ("4", "6.weight"), ("7", "9.weight")):
+            assert want[ln + ".bias"][17] != 0 and got[ln + ".bias"][17] != 0, ln
+            assert 2.0 ** -126 <= np.abs(got[nxt][:, 17]).max() < 2.0 ** -80, nxt
+
+
 def test_restatement_edge_cases(g, nets):
     x = g["states"][:40]
     rng = np.random.default_rng(3)
@@ -124,6 +155,26 @@ def test_restatement_edge_cases(g, nets):
     more = np.concatenate([x, g["states"][100:117]])
     c, Sc, _ = ref.backward(nets["actor"], more, np.concatenate([dz, np.zeros((17, 3))]))
     assert all(np.array_equal(c[k], a[k]) and np.array_equal(Sc[k], Sa[k]) for k in ref.KEYS)
+    # tests/test_gpu_mlp_backward_exact.py's identities 1 and 2, of the oracle itself: one live row gives the
+    # m = 1 result wherever it sits among rows with a zero head gradient, and the rows add up.  Within 4 G_CAP
+    # 2^-53 S < 1e-11 S, not bit for bit: a BLAS product may add a row's terms in another order at another m,
+    # which the forward's cancellation carries into S's units as it does in float32 (the docstring's G).
+    tol = 4.0 * G_CAP * 2.0 ** -53
+    singles = [ref.backward(nets["actor"], x[j:j + 1], dz[j:j + 1]) for j in range(40)]
+    for pos, j in ((0, 5), (16, 0), (39, 39), (17, 23)):
+        one = np.zeros((40, 3))
+        one[pos] = dz[j]
+        rows = x.copy()  # the dead rows keep their own states
+        rows[pos] = x[j]
+        e, Se, ne = ref.backward(nets["actor"], rows, one)
+        for k in ref.KEYS:
+            assert np.all(np.abs(e[k] - singles[j][0][k]) <= tol * singles[j][1][k]), (pos, j, k)
+            assert np.all(np.abs(Se[k] - singles[j][1][k]) <= tol * singles[j][1][k]), (pos, j, k)
+        assert abs(ne - singles[j][2]) <= 1e-9 * ne
+    for k in ref.KEYS:
+        total = sum(s[0][k] for s in singles)
+        assert np.all(np.abs(a[k] - total) <= 40 * tol * Sa[k]), k
+        assert np.all(np.abs(Sa[k] - sum(s[1][k] for s in singles)) <= 40 * tol * Sa[k]), k
     # the bias of the last Linear does not enter any gradient; a LayerNorm output is shift invariant
     sd = dict(nets["actor"])
     sd["9.bias"] = sd["9.bias"] + 5.0
