@@ -267,6 +267,22 @@ void dd_config_default(DDConfig *cfg);
 int dd_step(const DDConfig *cfg, const DDState *st, const DDStepIO *io,
             int64_t n, void *stream);
 
+/* dd_step_variant(): the kernel family a dd_step call takes. */
+enum { DD_STEP_GENERIC = 0, DD_STEP_FAST = 1 };
+
+/* Which kernel family dd_step takes for these arguments (its first chunk):
+ * DD_STEP_FAST, the kernel with the headline shape's switches compiled in,
+ * when the call has reference physics, the engine reward, bitmask actions,
+ * auto_reset, randomize_drone and randomize_platform on, a 16-byte aligned
+ * obs, no done_idx, no state_out, no shaped pointers, and n is a multiple of
+ * 256 and at most 262,144 (beyond it the kernel's extra `episode` load
+ * costs more than it saves);
+ * DD_STEP_GENERIC for every other call (n = 0 included); -1 for a null
+ * argument or an n dd_step refuses.  Both families compute the same bits.
+ * Host only: no GPU work, the pointers are not dereferenced. */
+int32_t dd_step_variant(const DDConfig *cfg, const DDState *st, const DDStepIO *io,
+                        int64_t n);
+
 /* `frames` consecutive frames in one launch (open-loop action sequences,
  * random-policy collection, PPO-shaped rollouts with known actions): the
  * same frame as dd_step, game_engine.py:95-138, applied frames times. */

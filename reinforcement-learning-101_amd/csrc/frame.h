@@ -223,16 +223,19 @@ __device__ __forceinline__ void spawn_words(const DDConfig& c, int64_t env, int3
 }
 
 // The re-spawn of a lane whose episode counter is already the new episode's,
-// from that episode's Philox block r (spawn_words).
+// from that episode's Philox block r (spawn_words).  kRandom: both spawn
+// switches are known to be on (the headline step kernel, step_fast.hip), so
+// neither is read; the ranges still come from c.
+template <bool kRandom = false>
 __device__ __forceinline__ void spawn_from(const DDConfig& c, double max_fuel, const uint32_t (&r)[4], Lane& s) {
-    if (c.randomize_drone) {
+    if (kRandom || c.randomize_drone) {
         s.x = draw_range(r[0], c.drone_x_min, (uint32_t)(c.drone_x_max - c.drone_x_min + 1));
         s.y = draw_range(r[1], c.drone_y_min, (uint32_t)(c.drone_y_max - c.drone_y_min + 1));
     } else {
         s.x = c.drone_start_x;
         s.y = c.drone_start_y;
     }
-    if (c.randomize_platform) {
+    if (kRandom || c.randomize_platform) {
         s.px = draw_range(r[2], c.platform_x_lo, (uint32_t)(c.platform_x_hi - c.platform_x_lo));
         s.py = draw_range(r[3], c.platform_y_lo, (uint32_t)(c.platform_y_hi - c.platform_y_lo));
     } else {
@@ -252,11 +255,12 @@ __device__ __forceinline__ void spawn_from(const DDConfig& c, double max_fuel, c
     s.dist = trig::sqrt_unscaled(dx * dx + dy * dy);
 }
 
+template <bool kRandom = false>
 __device__ __forceinline__ void spawn(const DDConfig& c, double max_fuel, int64_t env, Lane& s) {
     s.episode += 1;
     uint32_t r[4];
     spawn_words(c, env, s.episode, r);
-    spawn_from(c, max_fuel, r, s);
+    spawn_from<kRandom>(c, max_fuel, r, s);
 }
 
 // A rollout loop's re-spawns with the Philox block drawn ahead.  Under

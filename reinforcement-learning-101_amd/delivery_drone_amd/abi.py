@@ -17,7 +17,7 @@ __all__ = [
     "DD_ST_DONE", "DD_ST_LANDED", "DD_ST_CRASHED", "DD_ST_PLAT_LEFT", "DD_OBS_DIM",
     "DD_RENDER_HUD", "DD_RENDER_GAME_OVER", "DD_MLP_F32", "DD_MLP_F16X3",
     "DD_SHAPED_PPO", "DD_SHAPED_REINFORCE", "DD_ROLLOUT_AUTO", "DD_ROLLOUT_SINGLE", "DD_ROLLOUT_SPLIT_NO_WAIT",
-    "DD_ROLLOUT_FLUSHED", "DD_ROLLOUT_HELD", "DD_ROLLOUT_SPLIT", "DD_ERR_HANDOVER",
+    "DD_ROLLOUT_FLUSHED", "DD_ROLLOUT_HELD", "DD_ROLLOUT_SPLIT", "DD_STEP_GENERIC", "DD_STEP_FAST", "DD_ERR_HANDOVER",
     "DD_SAMPLE_BERNOULLI", "DD_SAMPLE_TEMPERED", "DD_SAMPLE_GREEDY",
     "DDConfig", "DDState", "DDStepIO", "DDRolloutIO", "DDMlpParams", "DDMlpIO", "DDPolicyRolloutIO", "DDSampling",
     "DDEpisodeStats", "DD_BATCH_GAE", "DD_BATCH_RETURNS", "DDBatchLayout", "DDBatchGatherIO", "DDBatchAdvIO",
@@ -42,6 +42,7 @@ DD_MLP_F32, DD_MLP_F16X3 = 0, 1
 DD_SHAPED_PPO, DD_SHAPED_REINFORCE = 0, 1
 DD_ROLLOUT_AUTO, DD_ROLLOUT_SINGLE, DD_ROLLOUT_SPLIT_NO_WAIT = 0, 1, 2
 DD_ROLLOUT_FLUSHED, DD_ROLLOUT_HELD, DD_ROLLOUT_SPLIT = 16, 17, 18
+DD_STEP_GENERIC, DD_STEP_FAST = 0, 1
 DD_ERR_HANDOVER = 1
 DD_MEM_DEFAULT, DD_MEM_CONTIGUOUS = 0, 1
 DD_SAMPLE_BERNOULLI, DD_SAMPLE_TEMPERED, DD_SAMPLE_GREEDY = 0, 1, 2
@@ -271,6 +272,8 @@ EXPORTS = {
     "dd_config_default": (None, [ctypes.POINTER(DDConfig)]),
     "dd_step": (ctypes.c_int, [ctypes.POINTER(DDConfig), ctypes.POINTER(DDState),
                                ctypes.POINTER(DDStepIO), ctypes.c_int64, ctypes.c_void_p]),
+    "dd_step_variant": (ctypes.c_int32, [ctypes.POINTER(DDConfig), ctypes.POINTER(DDState),
+                                         ctypes.POINTER(DDStepIO), ctypes.c_int64]),
     "dd_rollout": (ctypes.c_int, [ctypes.POINTER(DDConfig), ctypes.POINTER(DDState),
                                   ctypes.POINTER(DDRolloutIO), ctypes.c_int64, ctypes.c_void_p]),
     "dd_rollout_kernel": (ctypes.c_int, [ctypes.POINTER(DDConfig), ctypes.POINTER(DDState),
@@ -363,7 +366,7 @@ EXPORTS = {
 
 #: symbols a timing-only lab build (tools/build_variants.sh) or an older
 #: committed source built for an A/B run may lack
-_LAB_OPTIONAL = ("dd_build_info", "dd_selftest_sqrt", "dd_rollout_kernel", "dd_device_errors", "dd_stamp",
+_LAB_OPTIONAL = ("dd_build_info", "dd_selftest_sqrt", "dd_rollout_kernel", "dd_step_variant", "dd_device_errors", "dd_stamp",
                  "dd_wall_clock_khz", "dd_device_alloc", "dd_device_free", "dd_mlp_forward_sampled",
                  "dd_policy_rollout_sampled", "dd_batch_workspace", "dd_batch_plan", "dd_batch_gather",
                  "dd_batch_advantages", "dd_batch_normalize", "dd_episodes_workspace", "dd_episodes_count",

@@ -6,7 +6,11 @@ summary can be tied to the exact code it was measured on (bench.py compares
 the row's kernel hash before reporting roofline.traffic /
 rollout_point.traffic).
 
-    python tools/build_info.py step.s rollout.s policy_rollout.s > build_info.cpp"""
+    python tools/build_info.py step.s rollout.s policy_rollout.s [step_fast.s] > build_info.cpp
+
+With step_fast.s (the headline shape's own kernel, csrc/step_fast.hip) the
+string also carries step_fast_kernel_isa, so a counter row of that kernel is
+tied to its code and not to the generic step kernels'."""
 import hashlib
 import re
 import sys
@@ -57,10 +61,12 @@ def kernel_digest(path: str, prefix: bytes) -> str:
     return h.hexdigest()[:16]
 
 
-def main(step_isa: str, rollout_isa: str, policy_rollout_isa: str) -> None:
+def main(step_isa: str, rollout_isa: str, policy_rollout_isa: str, step_fast_isa: str = "") -> None:
     info = (f";step_isa={digest(step_isa)};policy_rollout_isa={digest(policy_rollout_isa)}"
             f";step_kernel_isa={kernel_digest(step_isa, b'_ZN2dd11step_kernel')}"
             f";rollout_kernel_isa={kernel_digest(rollout_isa, b'_ZN2dd14rollout_kernel')}")
+    if step_fast_isa:
+        info += f";step_fast_kernel_isa={kernel_digest(step_fast_isa, b'_ZN2dd16step_fast_kernel')}"
     print('#include "dronestep.h"')
     print("#define DD_STR2(x) #x")
     print("#define DD_STR(x) DD_STR2(x)")
@@ -68,4 +74,4 @@ def main(step_isa: str, rollout_isa: str, policy_rollout_isa: str) -> None:
 
 
 if __name__ == "__main__":
-    main(*sys.argv[1:4])
+    main(*sys.argv[1:5])

@@ -7,9 +7,11 @@ FETCH_SIZE counts each 128-B fabric read request as 64 B, so the read bytes
 are 2 x FETCH_SIZE x 1024; WRITE_SIZE x 1024 are the written bytes.  The two
 counters come from separate passes (FETCH_SIZE needs 3 TCC slots, WRITE_SIZE 2).
 
-    python tools/pmc_summary.py OUT.json [--rollout FRAMES] ENVS PRECISION OBS FETCH.csv WRITE.csv [...]
+    python tools/pmc_summary.py OUT.json [--rollout FRAMES | --kernel NAME] ENVS PRECISION OBS FETCH.csv WRITE.csv [...]
 
-(--rollout FRAMES: the passes are of dd_rollout launches of FRAMES frames, rollout_kernel rows)
+(--rollout FRAMES: the passes are of dd_rollout launches of FRAMES frames, rollout_kernel rows;
+--kernel NAME: rows of another dd_step kernel family, e.g. step_fast_kernel, kept under that name so
+bench.py's step_kernel lookup never takes them for the generic kernel's)
 
 Each row records the library's dd_build_info() (ABI version + step-kernel ISA
 hash) of the build the passes ran on — the in-tree libdronestep.so, which is
@@ -43,6 +45,8 @@ def main():
     kernel, frames = "step_kernel", None
     if args[:1] == ["--rollout"]:  # --rollout FRAMES: rows of dd_rollout launches of FRAMES frames
         kernel, frames, args = "rollout_kernel", int(args[1]), args[2:]
+    elif args[:1] == ["--kernel"]:  # --kernel NAME: rows of another dd_step kernel family
+        kernel, args = args[1], args[2:]
     try:
         doc = json.load(open(out))
     except (OSError, ValueError):
