@@ -140,15 +140,17 @@ constexpr Consts make_consts(const DDConfig& c) {
 // spills).  Switches, spawn ranges, wind and seed always come from the call.
 __device__ constexpr Consts kRefConsts = make_consts(reference_config());
 
-// True when every double the frame reads (wind aside) equals config.py's
+// True when every double the frame and the observation read (gravity ..
+// angle_scale, DDConfig's whole run of doubles; wind aside) equals config.py's
 // and the run has neither wind nor a moving platform: the kernels' kRef
-// instantiation, whose frame compiles neither in.
+// instantiation, whose frame compiles neither in.  angle_scale counts: the
+// kRef kernels' observe_values divides by kRefConsts' 180.
 inline bool uses_reference_physics(const DDConfig& c) {
     if (c.wind_enabled || c.platform_moving) return false;
     const DDConfig r = reference_config();
     const double* a = &c.gravity;
     const double* b = &r.gravity;
-    const int n = (int)((&c.vel_scale - &c.gravity) + 1);
+    const int n = (int)((&c.angle_scale - &c.gravity) + 1);
     for (int j = 0; j < n; ++j) {
         if (a + j == &c.wind_x || a + j == &c.wind_y) continue;
         if (memcmp(a + j, b + j, sizeof(double)) != 0) return false;

@@ -20,7 +20,12 @@ and ``dd_policy_rollout`` (the same, with the actor's sampled actions), under
 config.py's physics (the compiled-in ``kRef`` frame) and under a
 non-reference config (wind, and a ground level past the top out-of-bounds
 edge, so y' = world_height + margin decides: the kernarg frame's own risky
-tests)."""
+tests), and under a config that moves every landing boundary off config.py's
+("limits": speed 2.3, angle 12.5, pad 35 x 6, bottom centre 14 below the
+drone, margin 35, with wind), where the kernarg frame's near-boundary redo
+must follow the call's limits; tests/threshold_states.py places the states at
+the config's own boundaries.  The oracle alone shows the guards below hold
+for it (all states within 16.5 ulps; 28-31 % landed, 24-26 % crashed)."""
 import numpy as np
 import pytest
 import torch
@@ -34,10 +39,16 @@ from oracle import oracle as ora
 pytestmark = pytest.mark.gpu
 
 N = 1 << 20
+LANES = {"limits": 1 << 18}  # (the first two configs keep N)
+SEED_OFFSET = {"ref": 0, "wind_deep": 100, "limits": 200}
 CONFIGS = {
     "ref": dict(),
     # not config.py's physics: wind on, and the ground below the top edge
     "wind_deep": dict(wind_enabled=True, wind_x=0.0125, wind_y=-0.03125, ground_level=660),
+    # every landing limit, the pad, the drone's height and the margin away from config.py's
+    "limits": dict(wind_enabled=True, wind_x=0.0125, wind_y=-0.03125, max_landing_velocity=2.3,
+                   max_landing_angle=12.5, platform_half_width=35, platform_half_height=6, drone_half_height=14,
+                   oob_margin=35),
 }
 
 
@@ -57,14 +68,15 @@ def _actor(dev):
 @pytest.mark.parametrize("precision", ["f64", "f32"])
 def test_flags_exact_near_every_boundary(precision, cfg_name, path, gpu_device):
     cfg = EnvConfig(**CONFIGS[cfg_name])
-    seed = {"f64": 11, "f32": 12}[precision] + (100 if cfg_name != "ref" else 0)
-    st, acts, fam, dist = ts.generate(N, precision, seed=seed, config=cfg)
+    seed = {"f64": 11, "f32": 12}[precision] + SEED_OFFSET[cfg_name]
+    n = LANES.get(cfg_name, N)
+    st, acts, fam, dist = ts.generate(n, precision, seed=seed, config=cfg)
     assert np.mean(dist <= 16.5) > 0.99  # the states are where they should be
-    env = VecDroneEnv(N, device=gpu_device, precision=precision, config=cfg)
+    env = VecDroneEnv(n, device=gpu_device, precision=precision, config=cfg)
     dt = torch.float64 if precision == "f64" else torch.float32
     env.load_state_dict({f: torch.as_tensor(st[f], dtype=dt if f in gd.FLOAT_FIELDS else None)
                          for f in gd.FLOAT_FIELDS + ("status", "steps", "episode")})
-    o = ora.OracleEnv(N, precision=precision, config=cfg)
+    o = ora.OracleEnv(n, precision=precision, config=cfg)
     o.load_state_dict({f: (st[f].astype(np.float32) if precision == "f32" and f in gd.FLOAT_FIELDS else st[f])
                        for f in st})
     a_dev = torch.as_tensor(acts, device=gpu_device)
@@ -83,7 +95,7 @@ def test_flags_exact_near_every_boundary(precision, cfg_name, path, gpu_device):
     assert not bad.any(), f"flag mismatches per family: {report}"
     landed = (o.status & gd.ST_LANDED) != 0
     crashed = (o.status & gd.ST_CRASHED) != 0
-    assert landed.sum() > N // 50 and crashed.sum() > N // 20 and (~(landed | crashed)).sum() > N // 20
+    assert landed.sum() > n // 50 and crashed.sum() > n // 20 and (~(landed | crashed)).sum() > n // 20
     term = odone
     np.testing.assert_array_equal(g_reward[term], oreward[term].astype(np.float64))
     if precision == "f64":

@@ -39,13 +39,13 @@ STEP_FORMATS = ("bitmask", "f32x3", "u8x3")
 ROLLOUT_FORMATS = STEP_FORMATS + ("philox",)
 OTHER_PHYSICS = tuple(p for p in PHYSICS if p != "reference")
 
-# the fields uses_reference_physics compares: DDConfig gravity .. vel_scale but wind_x / wind_y
+# the fields uses_reference_physics compares: DDConfig gravity .. angle_scale (every double) but wind_x / wind_y
 _PHYSICS_FIELDS = ("gravity", "drag", "angular_drag", "main_thrust_power", "side_thrust_power", "fuel_main",
                    "fuel_side", "max_fuel", "drone_half_height", "dt", "platform_half_width", "platform_half_height",
                    "platform_speed", "platform_min_x", "platform_max_x", "max_landing_velocity", "max_landing_angle",
                    "world_width", "world_height", "oob_margin", "ground_level", "reward_step", "reward_landing",
                    "reward_crash", "reward_out_of_fuel", "reward_out_of_bounds", "shaping_offset", "shaping_scale",
-                   "vel_scale")
+                   "vel_scale", "angle_scale")
 
 StepKey = namedtuple("StepKey", "name T afmt ref shape")
 RolloutKey = namedtuple("RolloutKey", "T afmt ref held shape split")
@@ -219,7 +219,7 @@ def test_reference_physics_rule():
     for p in OTHER_PHYSICS:
         assert not uses_reference_physics(config_of(p)), p
     assert not uses_reference_physics(EnvConfig(angle_scale=180.0, vel_scale=10.5))
-    assert uses_reference_physics(EnvConfig(angle_scale=90.0))  # past vel_scale: not physics
+    assert not uses_reference_physics(EnvConfig(angle_scale=90.0))  # the observation's column 4 divides by it
 
 
 @pytest.mark.parametrize("case", rollout_matrix(), ids=rollout_id)

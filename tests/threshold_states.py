@@ -12,6 +12,10 @@ Families (each a share of the batch), the boundary and the variable moved:
   angle       |angle'| = 20 on the pad                 angle
   pad_x       bottom-centre x' = px -/+ 50, slow, upright   x
   pad_y       bottom-centre y' = py -/+ 10, slow, upright   y
+              (3, 20, 50 and 10 are config.py's: the boundaries are the
+              config's max_landing_velocity, max_landing_angle,
+              platform_half_width and platform_half_height, and the hover
+              height its drone_half_height)
   fuel        fuel' = 0 (fuel 0-3 with every action)   (exact)
 
 Targets are boundary + k ulps, k uniform in [-4, 4], in the storage width's
@@ -49,29 +53,37 @@ def _base(rng, n):
     return st, acts
 
 
-def _near_pad(rng, st, idx):
-    """Slow, upright drones hovering over their pad (the landing branch)."""
+def _near_pad(rng, st, idx, cfg):
+    """Slow, upright drones hovering over their pad (the landing branch):
+    inside the config's landing angle and pad extents, the bottom centre
+    (drone_half_height below the drone) about the pad's height.  Under
+    config.py's values the ranges are +-15 degrees, +-45 and -10 +- 8."""
     m = idx.size
-    ang = rng.uniform(-15, 15, m)
+    amax = 0.75 * float(cfg.max_landing_angle)
+    half_w, half_h = float(cfg.platform_half_width) - 5, float(cfg.platform_half_height) - 2
+    ang = rng.uniform(-amax, amax, m)
     st["angle"][idx] = ang
     st["omega"][idx] = rng.uniform(-0.5, 0.5, m)
     st["vx"][idx] = rng.uniform(-1.5, 1.5, m)
     st["vy"][idx] = rng.uniform(-2.0, 1.0, m)
-    st["x"][idx] = st["px"][idx] + rng.uniform(-45, 45, m)
-    st["y"][idx] = st["py"][idx] - 10 + rng.uniform(-8, 8, m)
+    st["x"][idx] = st["px"][idx] + rng.uniform(-half_w, half_w, m)
+    st["y"][idx] = st["py"][idx] - float(cfg.drone_half_height) + rng.uniform(-half_h, half_h, m)
 
 
 def generate(n: int, precision: str, seed: int = 0, iters: int = 6, config=None):
     """(state dict, actions u8 [n], family index [n], distance in storage ulps
     [n]) with the targeted quantity within ~4 storage ulps of its boundary,
     under `config` (default config.py's; the boundaries follow its
-    ground_level, oob_margin and world size, and the oracle probe its wind)."""
+    ground_level, oob_margin, world size, landing limits and pad extents, the
+    speed's Newton step its drag, and the oracle probe all of it)."""
     from oracle import oracle as ora
     from delivery_drone_amd import EnvConfig
 
     cfg = config or EnvConfig()
     ground, margin = float(cfg.ground_level), float(cfg.oob_margin)
     top = float(cfg.world_height) + margin
+    vmax, amax = float(cfg.max_landing_velocity), float(cfg.max_landing_angle)
+    half_w, half_h = float(cfg.platform_half_width), float(cfg.platform_half_height)
     rng = np.random.default_rng(seed)
     st, acts = _base(rng, n)
     fam = rng.integers(0, len(FAMILIES), n)
@@ -90,7 +102,7 @@ def generate(n: int, precision: str, seed: int = 0, iters: int = 6, config=None)
             st["y"][idx] = rng.uniform(g - 100, g + 90, m)
             st["vy"][idx] = rng.uniform(-1, 6, m)
             sel = rng.random(m) < 0.5  # half slow and upright: the on-pad crash tests
-            _near_pad(rng, st, idx[sel])
+            _near_pad(rng, st, idx[sel], cfg)
             st["py"][idx[sel]] = rng.integers(g - 5, g + 6, int(sel.sum()))
         elif name == "oob":
             sides = 4 if ground >= top else 3  # the top edge decides only past the ground
@@ -100,23 +112,23 @@ def generate(n: int, precision: str, seed: int = 0, iters: int = 6, config=None)
             var[idx] = np.where(side < 2, "x", "y")
             st["y"][idx[side == 3]] = rng.uniform(top - 40, top + 40, int((side == 3).sum()))
         elif name == "speed":
-            _near_pad(rng, st, idx)
-            col[idx], bound[idx], var[idx] = Q_SPEED, 3.0, "speed"
-            st["vx"][idx] = rng.uniform(-3, 3, m)
-            st["vy"][idx] = rng.uniform(-3, 3, m)
+            _near_pad(rng, st, idx, cfg)
+            col[idx], bound[idx], var[idx] = Q_SPEED, vmax, "speed"
+            st["vx"][idx] = rng.uniform(-vmax, vmax, m)
+            st["vy"][idx] = rng.uniform(-vmax, vmax, m)
         elif name == "angle":
-            _near_pad(rng, st, idx)
+            _near_pad(rng, st, idx, cfg)
             sign = np.where(rng.random(m) < 0.5, -1.0, 1.0)
-            col[idx], bound[idx], var[idx] = Q_ANGLE, 20.0 * sign, "angle"
-            st["angle"][idx] = 20.0 * sign
+            col[idx], bound[idx], var[idx] = Q_ANGLE, amax * sign, "angle"
+            st["angle"][idx] = amax * sign
         elif name == "pad_x":
-            _near_pad(rng, st, idx)
+            _near_pad(rng, st, idx, cfg)
             sign = np.where(rng.random(m) < 0.5, -1.0, 1.0)
-            col[idx], bound[idx], var[idx] = Q_BX, st["px"][idx] + 50.0 * sign, "x"
+            col[idx], bound[idx], var[idx] = Q_BX, st["px"][idx] + half_w * sign, "x"
         elif name == "pad_y":
-            _near_pad(rng, st, idx)
+            _near_pad(rng, st, idx, cfg)
             sign = np.where(rng.random(m) < 0.5, -1.0, 1.0)
-            col[idx], bound[idx], var[idx] = Q_BY, st["py"][idx] + 10.0 * sign, "y"
+            col[idx], bound[idx], var[idx] = Q_BY, st["py"][idx] + half_h * sign, "y"
         else:  # fuel: exact arithmetic, every action with 0-3 units left
             st["fuel"][idx] = rng.integers(0, 4, m)
             col[idx], bound[idx], var[idx] = Q_Y, np.nan, ""
@@ -139,13 +151,13 @@ def generate(n: int, precision: str, seed: int = 0, iters: int = 6, config=None)
         for v in ("x", "y", "angle"):
             sel = var == v
             st[v][sel] = st[v][sel] + err[sel]
-        # speed' = |0.99 (v + thrust + gravity)|: a Newton step on the larger
-        # post-update component (d speed' / d v = 0.99 v' / speed')
+        # speed' = |drag (v + thrust + gravity)|: a Newton step on the larger
+        # post-update component (d speed' / d v = drag v' / speed')
         sel = (var == "speed") & (cur > 0)
         vxp, vyp = q[:, Q_VX], q[:, Q_VY]
         use_x = np.abs(vxp) >= np.abs(vyp)
         comp = np.where(use_x, vxp, vyp)
-        step = np.where(sel & (comp != 0), err * cur / (0.99 * np.where(comp != 0, comp, 1.0)), 0.0)
+        step = np.where(sel & (comp != 0), err * cur / (float(cfg.drag) * np.where(comp != 0, comp, 1.0)), 0.0)
         st["vx"] = np.where(sel & use_x, st["vx"] + step, st["vx"])
         st["vy"] = np.where(sel & ~use_x, st["vy"] + step, st["vy"])
         quantize()
