@@ -638,7 +638,7 @@ int dd_policy_evaluate_parts(const DDConfig *cfg, const DDState *st, const float
  * pygame's primitives are restated (render.hip's header), not pixel-verified:
  * pygame is absent here, and the text uses DejaVu Sans Bold for pygame's
  * bundled font. */
-enum { DD_RENDER_HUD = 1, DD_RENDER_GAME_OVER = 2 };
+enum { DD_RENDER_HUD = 1, DD_RENDER_GAME_OVER = 2, DD_RENDER_LABELS = 4 /* dd_render_grid only */ };
 
 /* Renders `count` frames into rgb: uint8 [count][H][W][3].  The SoA holds n
  * lanes.  lanes: int32 [count] device indices into it, or NULL for lanes
@@ -650,6 +650,24 @@ enum { DD_RENDER_HUD = 1, DD_RENDER_GAME_OVER = 2 };
 int dd_render(const DDConfig *cfg, const DDState *st, const uint8_t *actions,
               const int32_t *lanes, int64_t count, int64_t n, uint8_t *rgb,
               int32_t flags, void *stream);
+
+/* The composite of socket_server.py --render-all (:155-225): the same `count`
+ * frames as tiles of one surface, rgb: uint8 [rows * H][cols * W][3].  Slot
+ * k < count is the tile at row k / cols, column k % cols, and holds exactly
+ * dd_render's frame k for the same arguments; the frame is stored straight
+ * into the mosaic (no intermediate, no second pass).  With DD_RENDER_LABELS,
+ * "Game {lane}" (the reference's game id; pygame.font.Font(None, 36), yellow)
+ * is blended over each tile with its top left at (10, 10) of the tile, after
+ * the HUD and the game-over overlay.  Unlike pygame, which clips to the whole
+ * surface, the label is clipped to its own tile (visible only where a tile is
+ * narrower than its label and the next tile is empty).  Every byte of rgb is
+ * written: tiles count <= k < rows * cols are all zero, and so is, without a
+ * label, a slot whose lane is outside [0, n).  Checks what dd_render checks,
+ * and cols >= 1, rows >= 1, count <= rows * cols <= 65535; count == 0 blacks
+ * out the whole grid.  dd_render ignores DD_RENDER_LABELS. */
+int dd_render_grid(const DDConfig *cfg, const DDState *st, const uint8_t *actions,
+                   const int32_t *lanes, int64_t count, int64_t n,
+                   int32_t cols, int32_t rows, uint8_t *rgb, int32_t flags, void *stream);
 
 /* Algorithmic HBM bytes of one dd_step lane (the roofline byte model,
  * DESIGN.md §4): precision, action format, obs on/off. */

@@ -32,6 +32,19 @@
 // sin / cos of the angle, so the CPU restatement (oracle/render.py) gets the
 // same pixels; numbers in the HUD are formatted like Python's f-strings
 // (correctly rounded, ties to even).
+//
+// dd_render_grid: the composite of socket_server.py --render-all (:155-225),
+// every game's frame as a tile of one surface, `cols` tiles to a row, each
+// with a yellow "Game {idx}" (Font(None, 36): font::kLabel*, 24 px) at
+// (x + 10, y + 10) of its tile; tiles without a game stay black.  It is the
+// same kernel instantiated with a tile origin and the mosaic's row pitch in
+// the store address: one grid row per tile, the same 12-byte stores, no
+// [count][H][W][3] intermediate.  The label is an eleventh string, drawn last
+// (over the HUD and the game-over overlay, so it is not darkened).  One
+// departure from pygame: a tile's pixels are evaluated in tile coordinates,
+// so the label is clipped to its own tile, where pygame clips to the whole
+// surface; it shows only when a tile is narrower than its label and the tile
+// to its right is empty.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -45,7 +58,9 @@ namespace render {
 constexpr int kBlock = 256;
 constexpr int kPix = 4;    // consecutive pixels per lane and pass (12 output bytes)
 constexpr int kQuads = 8;  // passes per lane: a block covers kBlock * kPix * kQuads = 8,192 pixels
-constexpr int kTexts = 10;
+constexpr int kTexts = 10;  // strings of a frame; a grid tile has one more, its label (string kLabel)
+constexpr int kLabel = 10;
+constexpr int kLabelFace = 3;
 constexpr int kMaxChars = 32;
 constexpr double kDeg2Rad = 3.14159265358979323846 / 180.0;
 
@@ -61,10 +76,11 @@ constexpr int kDroneW = 40;  // config.DRONE_WIDTH (the sprite; the physics neve
 // One string of the frame, laid out: its chars, the glyph and left edge of
 // each, and (built per block) the char under every column of its box.
 constexpr int kMaxTextW = 640;
-// The fixed text of each string (index 10: the title of a crash).
-__device__ constexpr char kPrefix[11][20] = {"Fuel: ", "Speed: ", "Angle: ", "Distance: ", "Episode: ",
+constexpr int kLabelW = 256;  // "Game " and the ten digits of an int32 are 255 px
+// The fixed text of each string (index 10: the title of a crash; 11: a grid tile's label).
+__device__ constexpr char kPrefix[12][20] = {"Fuel: ", "Speed: ", "Angle: ", "Distance: ", "Episode: ",
                                              "Steps: ", "H", "SUCCESSFUL LANDING!", "Total Reward: ",
-                                             "Press R to restart", "CRASHED!"};
+                                             "Press R to restart", "CRASHED!", "Game "};
 
 struct Text {
     int32_t x0, y0, w, h, face, len;
@@ -142,16 +158,39 @@ __device__ __forceinline__ uint32_t darken(uint32_t d) { return (d >> 1) & 0x7F7
 
 // The font tables a block reads while laying out and drawing its strings,
 // copied to LDS once (the layout walks them char by char: from global
-// memory that was a chain of dependent loads per string).
+// memory that was a chain of dependent loads per string).  A frame's strings
+// use the atlas's three faces.  A grid tile's label has a face of its own
+// (font::kLabel*, numbered from 0): in a grid kernel's tables it is face
+// kLabelFace, its glyphs follow the frame's, and its offsets stay relative to
+// font::kLabelAtlas (a string is of one face: coverage_of picks the array).
+template <bool kGrid>
 struct FontLds {
-    int16_t index[font::kFaces * 128];
-    uint8_t advance[font::kGlyphs];
-    uint32_t offset[font::kGlyphs];
+    static constexpr bool kWithLabel = kGrid;
+    static constexpr int kFaces = font::kFaces + (kGrid ? 1 : 0);
+    static constexpr int kGlyphs = font::kGlyphs + (kGrid ? font::kLabelGlyphs : 0);
+    int16_t index[kFaces * 128];
+    uint8_t advance[kGlyphs];
+    uint32_t offset[kGlyphs];
 };
+static_assert(kLabelFace == font::kFaces, "the label's face follows the atlas's");
+
+template <bool kGrid>
+__device__ __forceinline__ int face_height(int face) {
+    if (kGrid && face == kLabelFace) return font::kLabelHeight;
+    return font::kHeight[face];
+}
+
+// the coverage bytes a string's glyph offsets index
+template <bool kGrid>
+__device__ __forceinline__ const uint8_t* coverage_of(const Text& t) {
+    if (kGrid && t.face == kLabelFace) return font::kLabelAtlas;
+    return font::kAtlas;
+}
 
 // string t blended over colour d at pixel (X, Y) (pygame ALPHA_BLEND of the
 // glyph's coverage); d unchanged outside its box
-__device__ __forceinline__ uint32_t draw_text(uint32_t d, const Text& t, const uint8_t* cc, const FontLds& fl,
+template <typename Font>
+__device__ __forceinline__ uint32_t draw_text(uint32_t d, const Text& t, const uint8_t* cc, const Font& fl,
                                               const uint8_t* raster, int X, int Y) {
     const int u = X - t.x0, v = Y - t.y0;
     if (u < 0 || u >= t.w || v < 0 || v >= t.h || t.len == 0) return d;
@@ -161,29 +200,30 @@ __device__ __forceinline__ uint32_t draw_text(uint32_t d, const Text& t, const u
     } else {  // did not fit the raster: from the atlas
         const int i = cc[u];
         const int g = t.glyph[i];
-        a = font::kAtlas[fl.offset[g] + v * fl.advance[g] + (u - t.start[i])];
+        a = coverage_of<Font::kWithLabel>(t)[fl.offset[g] + v * fl.advance[g] + (u - t.start[i])];
     }
     return a ? blend(d, t.color, a) : d;
 }
 
 // the strings of `mask` over a lane's 4 pixels (X0 .. X0 + 3, row Y), each
 // only where its rows and columns meet them
+template <typename Font>
 __device__ __forceinline__ void draw_texts(uint32_t (&px4)[kPix], uint32_t mask, const Text* texts,
-                                           const uint8_t (*colchar)[kMaxTextW], const FontLds& fl,
-                                           const uint8_t* raster, int X0, int Y) {
+                                           const uint8_t* colchar, const Font& fl, const uint8_t* raster, int X0,
+                                           int Y) {
     for (uint32_t m = mask; m; m &= m - 1) {
         const int k = __builtin_ctz(m);
         const Text& t = texts[k];
         if (Y < t.y0 || Y >= t.y0 + t.h || X0 + kPix <= t.x0 || X0 >= t.x0 + t.w) continue;
 #pragma unroll
-        for (int j = 0; j < kPix; ++j) px4[j] = draw_text(px4[j], t, colchar[k], fl, raster, X0 + j, Y);
+        for (int j = 0; j < kPix; ++j) px4[j] = draw_text(px4[j], t, colchar + k * kMaxTextW, fl, raster, X0 + j, Y);
     }
 }
 
 struct Args {
     const uint8_t* actions;  // [N] bitmask of the last step (nullable: no flames)
     const int32_t* lanes;    // [count] lanes to draw (nullable: 0..count-1)
-    uint8_t* rgb;            // [count][H][W][3]
+    uint8_t* rgb;            // [count][H][W][3]; a grid: [rows * H][cols * W][3]
     int32_t width, height, ground, count;
     int64_t n;               // lanes in the SoA
     int32_t phw, phh, dhh;   // platform half width / height, drone half height (px)
@@ -197,19 +237,40 @@ struct View {
     const int32_t *steps, *episode;
 };
 
-template <typename T>
-__global__ __launch_bounds__(kBlock) void render_kernel(Args p, View<T> v) {
-    __shared__ Text texts[kTexts];
-    __shared__ uint8_t colchar[kTexts][kMaxTextW];
+// Where the 4 pixels t * kPix .. of slot's frame go: frame after frame, or
+// (kGrid) into tile (slot / cols, slot % cols) of a mosaic `cols` tiles wide,
+// whose rows are cols * W * 3 bytes apart.  64-bit: a mosaic can pass 2^31 bytes.
+template <bool kGrid>
+__device__ __forceinline__ uint32_t* quad_dst(const Args& p, int cols, int slot, int t) {
+    if constexpr (kGrid) {
+        const int Y = (t * kPix) / p.width, X0 = (t * kPix) - Y * p.width;
+        const size_t row = (size_t)(slot / cols) * p.height + Y, col = (size_t)(slot % cols) * p.width + X0;
+        return reinterpret_cast<uint32_t*>(p.rgb + (row * cols * p.width + col) * 3);
+    } else {
+        return reinterpret_cast<uint32_t*>(p.rgb + ((size_t)slot * p.width * p.height + (size_t)t * kPix) * 3);
+    }
+}
+
+// A block draws 8,192 pixels of one frame.  kGrid (dd_render_grid; grid.y =
+// rows * cols): the frame is tile `slot` of a mosaic `cols` tiles wide,
+// labelled (string kLabel) if DD_RENDER_LABELS is set, and tiles past p.count
+// are black.  The switch is compiled in: dd_render's kernels carry neither the
+// label nor the tile address, and never read `cols`.
+template <typename T, bool kGrid>
+__global__ __launch_bounds__(kBlock) void render_kernel(Args p, View<T> v, int32_t cols) {
+    constexpr int kStrings = kTexts + (kGrid ? 1 : 0);
+    __shared__ Text texts[kStrings];
+    __shared__ uint8_t colchar[kTexts * kMaxTextW + (kGrid ? kLabelW : 0)];  // string k's columns at k * kMaxTextW
     __shared__ uint8_t raster[kRaster];
-    __shared__ FontLds fl;
+    __shared__ FontLds<kGrid> fl;
     const int slot = blockIdx.y;
-    const int lane = p.lanes ? p.lanes[slot] : slot;
+    const bool tile = !kGrid || slot < p.count;  // (lanes holds p.count indices)
+    const int lane = !tile ? -1 : p.lanes ? p.lanes[slot] : slot;
     if (lane < 0 || lane >= p.n) {  // not a lane: an all-zero frame
         for (int q = 0; q < kQuads; ++q) {
             const int t = (blockIdx.x * kQuads + q) * kBlock + threadIdx.x;
             if (t * kPix < p.width * p.height) {
-                uint32_t* dst = reinterpret_cast<uint32_t*>(p.rgb + ((size_t)slot * p.width * p.height + (size_t)t * kPix) * 3);
+                uint32_t* dst = quad_dst<kGrid>(p, cols, slot, t);
                 __builtin_nontemporal_store(0u, dst);
                 __builtin_nontemporal_store(0u, dst + 1);
                 __builtin_nontemporal_store(0u, dst + 2);
@@ -262,8 +323,8 @@ __global__ __launch_bounds__(kBlock) void render_kernel(Args p, View<T> v) {
     const float reach = fmaxf(hw + hh + 1.0f, fmaxf(hh + 7.5f + 8.0f + 1.0f, hw + 5.0f + 5.0f + 1.5f));
     const bool blk_drone = ((float)row_hi + 0.5f) - yf >= -reach && ((float)row_lo + 0.5f) - yf <= reach;
     // string k: where (y0 follows from the face height alone) and whether it is drawn
-    int tx[kTexts], ty[kTexts], tface[kTexts];
-    bool ton[kTexts], tcentre[kTexts];
+    int tx[kStrings], ty[kStrings], tface[kStrings];
+    bool ton[kStrings], tcentre[kStrings];
     {
         const int hud_y[6] = {12, 40, 65, 90, 10, 35};
         const int hud_x[6] = {15, 10, 10, 10, W - 150, W - 150};
@@ -277,11 +338,15 @@ __global__ __launch_bounds__(kBlock) void render_kernel(Args p, View<T> v) {
         for (int k = 7; k < kTexts; ++k) {
             tx[k] = W / 2; ty[k] = over_y[k - 7]; tface[k] = k == 7 ? 2 : 0; ton[k] = over; tcentre[k] = true;
         }
+        if constexpr (kGrid) {  // the tile's label, top left at (10, 10) of the tile
+            tx[kLabel] = 10; ty[kLabel] = 10; tface[kLabel] = kLabelFace; tcentre[kLabel] = false;
+            ton[kLabel] = (p.flags & DD_RENDER_LABELS) != 0;
+        }
     }
     uint32_t need = 0;  // strings this block draws (wave-uniform)
 #pragma unroll
-    for (int k = 0; k < kTexts; ++k) {
-        const int h = font::kHeight[tface[k]];
+    for (int k = 0; k < kStrings; ++k) {
+        const int h = face_height<kGrid>(tface[k]);
         const int y0 = tcentre[k] ? ty[k] - h / 2 : ty[k];
         if (ton[k] && row_hi >= y0 && row_lo < y0 + h) need |= 1u << k;
     }
@@ -291,21 +356,32 @@ __global__ __launch_bounds__(kBlock) void render_kernel(Args p, View<T> v) {
             fl.advance[i] = font::kAdvance[i];
             fl.offset[i] = font::kOffset[i];
         }
+        if constexpr (kGrid) {  // the label's face, its glyphs numbered after the frame's
+            if (threadIdx.x < 128) {
+                const int g = font::kLabelIndex[threadIdx.x];
+                fl.index[kLabelFace * 128 + threadIdx.x] = (int16_t)(g < 0 ? -1 : font::kGlyphs + g);
+            }
+            if (threadIdx.x < font::kLabelGlyphs) {
+                fl.advance[font::kGlyphs + threadIdx.x] = font::kLabelAdvance[threadIdx.x];
+                fl.offset[font::kGlyphs + threadIdx.x] = font::kLabelOffset[threadIdx.x];
+            }
+        }
         __syncthreads();
         const int k = threadIdx.x;
-        if (k < kTexts && ((need >> k) & 1u)) {
+        if (k < kStrings && ((need >> k) & 1u)) {
             Text& t = texts[k];
             Str str{t.s, 0};
-            // One code path for all ten strings (they are laid out by ten lanes
-            // of one wave): prefix from a table, then at most one number.
+            // One code path for all the strings (they are laid out by ten or
+            // eleven lanes of one wave): prefix from a table, then at most one number.
             //   0 f"Fuel: {int(fuel)}"      (15, 12)   5 f"Steps: {steps}"     (W - 150, 35)
             //   1 f"Speed: {speed:.1f}"     (10, 40)   6 "H", centred on the pad
             //   2 f"Angle: {angle:.1f}°"    (10, 65)   7 game-over title, (W // 2, H // 2 - 30)
             //   3 f"Distance: {dist:.0f}"   (10, 90)   8 f"Total Reward: {total:.1f}" (W // 2, H // 2 + 20)
             //   4 f"Episode: {episode}"     (W - 150, 10)  9 "Press R to restart" (W // 2, H // 2 + 50)
+            //   10 (a grid tile) f"Game {lane}" (10, 10)
             const double vx = (double)v.vx[lane], vy = (double)v.vy[lane], dx = px - x, dy = py - y;
             const bool landed = (status & DD_ST_LANDED) != 0;
-            const int pre = k == 7 ? (landed ? 7 : 10) : k;
+            const int pre = k == 7 ? (landed ? 7 : 10) : (kGrid && k == kLabel) ? 11 : k;
             double num = 0.0;
             int decimals = -1;  // -1: no number; 0: integer or .0f; 1: .1f
             switch (k) {  // selects only: every lane runs the same instructions
@@ -318,10 +394,11 @@ __global__ __launch_bounds__(kBlock) void render_kernel(Args p, View<T> v) {
                 case 8: num = (double)v.total[lane]; decimals = 1; break;
                 default: break;
             }
+            if (kGrid && k == kLabel) { num = (double)lane; decimals = 0; }
             for (const char* c = kPrefix[pre]; *c; ++c) str.put(*c);
             if (decimals >= 0) str.put_fixed(num, decimals);
             if (k == 2) str.put((char)font::kDegree);
-            const uint32_t color = k != 7 ? kWhite : landed ? kGreen : kRed;
+            const uint32_t color = (kGrid && k == kLabel) ? kYellow : k != 7 ? kWhite : landed ? kGreen : kRed;
             const int face = tface[k];
             int w = 0, n = 0;
             for (int i = 0; i < str.n; ++i) {  // glyphs with a cell in this face, side by side
@@ -335,8 +412,8 @@ __global__ __launch_bounds__(kBlock) void render_kernel(Args p, View<T> v) {
             t.len = n;
             t.face = face;
             t.color = color;
-            t.h = font::kHeight[face];
-            t.w = min(w, kMaxTextW);
+            t.h = face_height<kGrid>(face);
+            t.w = min(w, (kGrid && k == kLabel) ? kLabelW : kMaxTextW);
             // get_rect(center=...): x = cx - w // 2, y = cy - h // 2
             t.x0 = tcentre[k] ? tx[k] - w / 2 : tx[k];
             t.y0 = tcentre[k] ? ty[k] - t.h / 2 : ty[k];
@@ -359,7 +436,7 @@ __global__ __launch_bounds__(kBlock) void render_kernel(Args p, View<T> v) {
             for (int u = threadIdx.x; u < t.w; u += kBlock) {
                 int i = 0;
                 while (i + 1 < t.len && t.start[i + 1] <= u) ++i;
-                colchar[k2][u] = (uint8_t)i;
+                colchar[k2 * kMaxTextW + u] = (uint8_t)i;
             }
         }
         __syncthreads();
@@ -369,9 +446,9 @@ __global__ __launch_bounds__(kBlock) void render_kernel(Args p, View<T> v) {
             if (t.roff < 0 || t.w == 0) continue;
             const int rows = max(0, min(t.y0 + t.h, row_hi + 1) - t.r0);
             for (int u = threadIdx.x; u < t.w; u += kBlock) {  // a column per lane: its rows loaded together
-                const int i = colchar[k2][u];
+                const int i = colchar[k2 * kMaxTextW + u];
                 const int adv = fl.advance[t.glyph[i]];
-                const uint8_t* src = font::kAtlas + fl.offset[t.glyph[i]] + (t.r0 - t.y0) * adv + (u - t.start[i]);
+                const uint8_t* src = coverage_of<kGrid>(t) + fl.offset[t.glyph[i]] + (t.r0 - t.y0) * adv + (u - t.start[i]);
                 for (int rb = 0; rb < rows; rb += kBlockRows) {
                     uint8_t col[kBlockRows];
 #pragma unroll
@@ -453,11 +530,12 @@ __global__ __launch_bounds__(kBlock) void render_kernel(Args p, View<T> v) {
             for (int j = 0; j < kPix; ++j) px4[j] = darken(px4[j]);
             draw_texts(px4, need & 0x380u, texts, colchar, fl, raster, X0, Y);
         }
+        if constexpr (kGrid) draw_texts(px4, need & (1u << kLabel), texts, colchar, fl, raster, X0, Y);  // last: not darkened
         // 4 RGB pixels = 3 dwords, little-endian byte order R G B R G B ...
         const uint32_t w0 = (px4[0] & 0xFFFFFFu) | (px4[1] << 24);
         const uint32_t w1 = ((px4[1] >> 8) & 0xFFFFu) | (px4[2] << 16);
         const uint32_t w2 = ((px4[2] >> 16) & 0xFFu) | (px4[3] << 8);
-        uint32_t* dst = reinterpret_cast<uint32_t*>(p.rgb + ((size_t)slot * W * H + (size_t)t0 * kPix) * 3);
+        uint32_t* dst = quad_dst<kGrid>(p, cols, slot, t0);
         __builtin_nontemporal_store(w0, dst);
         __builtin_nontemporal_store(w1, dst + 1);
         __builtin_nontemporal_store(w2, dst + 2);
@@ -477,21 +555,17 @@ View<T> view_of(const DDState& st) {
 // an integer-valued double in [lo, hi]
 inline bool whole(double d, double lo, double hi) { return d >= lo && d <= hi && d == (double)(int64_t)d; }
 
-}  // namespace render
-}  // namespace dd
-
-extern "C" int dd_render(const DDConfig* cfg, const DDState* st, const uint8_t* actions, const int32_t* lanes,
-                         int64_t count, int64_t n, uint8_t* rgb, int32_t flags, void* stream) {
-    using namespace dd::render;
-    if (!cfg || !st || count < 0 || n < 0 || (!lanes && count > n)) return (int)hipErrorInvalidValue;
-    if (count == 0) return 0;
+// The checks and the launch the two entry points share.  `tiles` frames are
+// written: `count` of them drawn; cols == 0 is dd_render (tiles == count, frame after frame).
+static int launch(const DDConfig* cfg, const DDState* st, const uint8_t* actions, const int32_t* lanes, int64_t count,
+                  int64_t n, int32_t cols, int64_t tiles, uint8_t* rgb, int32_t flags, void* stream) {
     if (!rgb || !st->x || !st->y || !st->vx || !st->vy || !st->angle || !st->fuel || !st->px || !st->py ||
         !st->total_reward || !st->status || !st->steps || !st->episode)
         return (int)hipErrorInvalidValue;
     if (!whole(cfg->world_width, 4, 16384) || !whole(cfg->world_height, 1, 16384) ||
         ((int64_t)cfg->world_width % 4) != 0 || !whole(cfg->ground_level, -1e6, 1e6) ||
         !whole(cfg->platform_half_width, 0, 4096) || !whole(cfg->platform_half_height, 0, 4096) ||
-        !whole(cfg->drone_half_height, 1, 64) || count > 65535)
+        !whole(cfg->drone_half_height, 1, 64) || tiles > 65535)
         return (int)hipErrorInvalidValue;
     Args p;
     p.actions = actions;
@@ -507,13 +581,35 @@ extern "C" int dd_render(const DDConfig* cfg, const DDState* st, const uint8_t* 
     p.dhh = (int32_t)cfg->drone_half_height;
     p.flags = flags;
     const int64_t quads = ((int64_t)p.width * p.height / kPix + kQuads - 1) / kQuads;
-    dim3 grid((unsigned)((quads + kBlock - 1) / kBlock), (unsigned)count);
+    dim3 grid((unsigned)((quads + kBlock - 1) / kBlock), (unsigned)tiles);
     hipStream_t s = (hipStream_t)stream;
-    if (st->precision == DD_F64)
-        render_kernel<double><<<grid, kBlock, 0, s>>>(p, view_of<double>(*st));
-    else if (st->precision == DD_F32)
-        render_kernel<float><<<grid, kBlock, 0, s>>>(p, view_of<float>(*st));
-    else
-        return (int)hipErrorInvalidValue;
+    if (st->precision != DD_F64 && st->precision != DD_F32) return (int)hipErrorInvalidValue;
+    const bool f64 = st->precision == DD_F64;
+    if (cols == 0) {
+        if (f64) render_kernel<double, false><<<grid, kBlock, 0, s>>>(p, view_of<double>(*st), 0);
+        else render_kernel<float, false><<<grid, kBlock, 0, s>>>(p, view_of<float>(*st), 0);
+    } else {
+        if (f64) render_kernel<double, true><<<grid, kBlock, 0, s>>>(p, view_of<double>(*st), cols);
+        else render_kernel<float, true><<<grid, kBlock, 0, s>>>(p, view_of<float>(*st), cols);
+    }
     return (int)hipGetLastError();
+}
+
+}  // namespace render
+}  // namespace dd
+
+extern "C" int dd_render(const DDConfig* cfg, const DDState* st, const uint8_t* actions, const int32_t* lanes,
+                         int64_t count, int64_t n, uint8_t* rgb, int32_t flags, void* stream) {
+    if (!cfg || !st || count < 0 || n < 0 || (!lanes && count > n)) return (int)hipErrorInvalidValue;
+    if (count == 0) return 0;
+    return dd::render::launch(cfg, st, actions, lanes, count, n, 0, count, rgb, flags, stream);
+}
+
+extern "C" int dd_render_grid(const DDConfig* cfg, const DDState* st, const uint8_t* actions, const int32_t* lanes,
+                              int64_t count, int64_t n, int32_t cols, int32_t rows, uint8_t* rgb, int32_t flags,
+                              void* stream) {
+    if (!cfg || !st || count < 0 || n < 0 || (!lanes && count > n)) return (int)hipErrorInvalidValue;
+    const int64_t tiles = (int64_t)rows * cols;
+    if (cols < 1 || rows < 1 || tiles > 65535 || count > tiles) return (int)hipErrorInvalidValue;
+    return dd::render::launch(cfg, st, actions, lanes, count, n, cols, tiles, rgb, flags, stream);  // count == 0: all black
 }

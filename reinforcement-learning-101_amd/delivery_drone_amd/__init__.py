@@ -28,10 +28,13 @@ learners: REINFORCE (:func:`collect_reinforce`, :func:`reinforce_losses`,
 :func:`reinforce_update`) and the one-step TD actor-critic
 (:func:`td_losses`, :func:`actor_critic_update`); and several actors in one
 fused launch, each on its own group of lanes (:class:`ActorPopulation`,
-:func:`population_summary`: a checkpoint tournament or a sweep's collection).
+:func:`population_summary`: a checkpoint tournament or a sweep's collection);
+and the frames of ``DroneGame.render`` (:meth:`VecDroneEnv.render`) and the
+labelled grid of ``--render-all`` (:meth:`VecDroneEnv.render_grid`,
+:func:`grid_shape`).
 """
 from .config import EnvConfig
-from .vec_env import OBS_KEYS, StepInfo, VecDroneEnv
+from .vec_env import OBS_KEYS, StepInfo, VecDroneEnv, grid_shape
 from .compat import DroneGame, DroneGameClient, DroneState, action_bits
 from .sharding import dist_env, gather_obs, shard_bounds
 from .gae import gae
@@ -47,7 +50,7 @@ from .pg_loss import ActorCriticUpdate, TdLosses, actor_critic_update, td_losses
 from .reward_parts import notebook_rewards
 
 __all__ = [
-    "EnvConfig", "VecDroneEnv", "StepInfo", "OBS_KEYS",
+    "EnvConfig", "VecDroneEnv", "StepInfo", "OBS_KEYS", "grid_shape",
     "DroneGame", "DroneGameClient", "DroneState", "action_bits",
     "shard_bounds", "dist_env", "gather_obs", "gae", "MlpNet",
     "ppo_batch", "reinforce_batch", "collect_ppo",

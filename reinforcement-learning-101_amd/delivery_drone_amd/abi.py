@@ -15,7 +15,7 @@ import torch  # noqa: F401  -- must be loaded first so the library binds torch's
 __all__ = [
     "DD_F32", "DD_F64", "DD_ACT_BITMASK", "DD_ACT_F32X3", "DD_ACT_U8X3", "DD_ACT_PHILOX",
     "DD_ST_DONE", "DD_ST_LANDED", "DD_ST_CRASHED", "DD_ST_PLAT_LEFT", "DD_OBS_DIM",
-    "DD_RENDER_HUD", "DD_RENDER_GAME_OVER", "DD_MLP_F32", "DD_MLP_F16X3",
+    "DD_RENDER_HUD", "DD_RENDER_GAME_OVER", "DD_RENDER_LABELS", "DD_MLP_F32", "DD_MLP_F16X3",
     "DD_SHAPED_PPO", "DD_SHAPED_REINFORCE", "DD_ROLLOUT_AUTO", "DD_ROLLOUT_SINGLE", "DD_ROLLOUT_SPLIT_NO_WAIT",
     "DD_ROLLOUT_FLUSHED", "DD_ROLLOUT_HELD", "DD_ROLLOUT_SPLIT", "DD_STEP_GENERIC", "DD_STEP_FAST", "DD_ERR_HANDOVER",
     "DD_SAMPLE_BERNOULLI", "DD_SAMPLE_TEMPERED", "DD_SAMPLE_GREEDY",
@@ -37,7 +37,7 @@ DD_F32, DD_F64 = 0, 1
 DD_ACT_BITMASK, DD_ACT_F32X3, DD_ACT_U8X3, DD_ACT_PHILOX = 0, 1, 2, 3
 DD_ST_DONE, DD_ST_LANDED, DD_ST_CRASHED, DD_ST_PLAT_LEFT = 1, 2, 4, 8
 DD_OBS_DIM = 15
-DD_RENDER_HUD, DD_RENDER_GAME_OVER = 1, 2
+DD_RENDER_HUD, DD_RENDER_GAME_OVER, DD_RENDER_LABELS = 1, 2, 4
 DD_MLP_F32, DD_MLP_F16X3 = 0, 1
 DD_SHAPED_PPO, DD_SHAPED_REINFORCE = 0, 1
 DD_ROLLOUT_AUTO, DD_ROLLOUT_SINGLE, DD_ROLLOUT_SPLIT_NO_WAIT = 0, 1, 2
@@ -314,6 +314,9 @@ EXPORTS = {
     "dd_render": (ctypes.c_int, [ctypes.POINTER(DDConfig), ctypes.POINTER(DDState), ctypes.c_void_p,
                                  ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_void_p, _I,
                                  ctypes.c_void_p]),
+    "dd_render_grid": (ctypes.c_int, [ctypes.POINTER(DDConfig), ctypes.POINTER(DDState), ctypes.c_void_p,
+                                      ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, _I, _I, ctypes.c_void_p, _I,
+                                      ctypes.c_void_p]),
     "dd_step_bytes_per_env": (ctypes.c_int64, [_I, _I, _I]),
     "dd_error_string": (ctypes.c_char_p, [ctypes.c_int]),
     "dd_abi_version": (ctypes.c_int, []),
@@ -374,7 +377,7 @@ _LAB_OPTIONAL = ("dd_build_info", "dd_selftest_sqrt", "dd_rollout_kernel", "dd_s
                  "dd_ppo_loss_workspace", "dd_ppo_losses", "dd_mlp_backward_workspace", "dd_mlp_backward",
                  "dd_adamw_state_bytes", "dd_adamw_init", "dd_adamw_step", "dd_pg_loss_workspace", "dd_pg_losses",
                  "dd_td_loss_workspace", "dd_td_losses", "dd_shuffle_indices", "dd_shuffle_rows",
-                 "dd_policy_evaluate_parts", "dd_policy_rollout_population")
+                 "dd_policy_evaluate_parts", "dd_policy_rollout_population", "dd_render_grid")
 
 
 class NativeLibraryError(RuntimeError):
