@@ -1185,6 +1185,83 @@ typedef struct DDShuffleIO {
 int dd_shuffle_indices(int64_t m, uint64_t seed, uint64_t epoch, int32_t *out, void *stream);
 int dd_shuffle_rows(const DDShuffleIO *io, int64_t m, uint64_t seed, uint64_t epoch, void *stream);
 
+/* ---- PPO's minibatch epochs in one launch (additions to ABI 13) --------------
+ * The training cell's `for epoch: for minibatch:` loop for minibatches of at
+ * most DD_PPO_FUSED_ROWS rows (dd_mlp_backward's row tile) and DD_MLP_F32
+ * networks: for e in [0, num_epochs) and minibatch i of the epoch, in that
+ * order, exactly what these calls do on rows [first, first + rows) with first =
+ * e epoch_stride + i minibatch_size, rows = min(minibatch_size, m - i
+ * minibatch_size):
+ *   dd_mlp_evaluate_actions (actor) and dd_mlp_forward (critic) on the rows,
+ *   dd_ppo_losses with both gradients,
+ *   dd_mlp_backward of each network with max_norm = max_grad_norm,
+ *   dd_adamw_step of each network with its packed image,
+ * bit for bit: parameters, moments, state blocks, packed images and logs.  One
+ * persistent kernel of two 256-thread workgroups, one per network (total_loss
+ * separates: the actor's gradient needs the actor alone, the critic's the
+ * critic), each walking the minibatches in order with its forward, loss sums,
+ * backward tile, norm, clip, AdamW step and re-pack; then one small kernel that
+ * forms total_loss from both.  The number of launches does not depend on m /
+ * minibatch_size, and nothing is read back.
+ *
+ * The epochs' rows: epoch e reads rows [e epoch_stride, e epoch_stride + m) of
+ * every column, so the caller lays out num_epochs shuffled copies of the batch
+ * (dd_shuffle_rows with epoch + e, epoch_stride >= m), or passes epoch_stride =
+ * 0 and every epoch reads the same rows.  The minibatches of an epoch are i =
+ * 0 .. steps - 1 with steps = ceil(m / minibatch_size), or floor(m /
+ * minibatch_size) when drop_last.
+ * logs: [DD_PPO_FUSED_LOGS][num_epochs][steps] doubles: rows DD_PPO_TOTAL_LOSS
+ * .. DD_PPO_CLIPPED_FRAC as dd_ppo_losses' result, then the actor's and the
+ * critic's gradient norm before clipping.
+ * grads: each network's flat gradient buffer, left holding the last
+ * minibatch's clipped gradient.  max_grad_norm as DDMlpBackwardIO's max_norm.
+ * workspace: dd_ppo_update_fused_workspace() bytes, 16-byte aligned.
+ * hipErrorInvalidValue, before any launch: a null io, workspace, column, logs
+ * or network buffer; a state that is not 8-byte or a packed or workspace that
+ * is not 16-byte aligned; ln_eps <= 0; hyper-parameters dd_adamw_step refuses;
+ * m < 1 or m >= 2^31; minibatch_size outside [1, DD_PPO_FUSED_ROWS]; num_epochs
+ * < 1; no minibatch (drop_last with m < minibatch_size); epoch_stride negative,
+ * or positive and below m; an unknown action_format; a clip_epsilon that is
+ * negative or not finite; a coefficient that is not finite; a NaN
+ * max_grad_norm. */
+#define DD_PPO_FUSED_ROWS 128
+enum { DD_PPO_POLICY_GRAD_NORM = 9, DD_PPO_CRITIC_GRAD_NORM = 10, DD_PPO_FUSED_LOGS = 11 };
+typedef struct DDPpoFusedNet {
+    float *params;         /* [27456 + 65 K], updated in place               */
+    float *grads;          /* same length, scratch                           */
+    float *exp_avg;        /* same length                                    */
+    float *exp_avg_sq;     /* same length                                    */
+    DDAdamWState *state;   /* the optimizer's device block                   */
+    float *packed;         /* the network's DD_MLP_F32 dd_mlp_pack image     */
+    DDAdamWHyper hyper;
+    float ln_eps;
+    int32_t _pad;
+} DDPpoFusedNet;
+
+typedef struct DDPpoFusedIO {
+    DDPpoFusedNet actor;         /* K = 3                                     */
+    DDPpoFusedNet critic;        /* K = 1                                     */
+    const float *states;         /* [epochs' rows][15]                        */
+    const void *actions;         /* uint8 [rows] or float [rows][3]           */
+    const float *old_log_probs;  /* [rows]                                    */
+    const float *advantages;     /* [rows]                                    */
+    const float *returns;        /* [rows]                                    */
+    int32_t action_format;       /* DD_ACT_BITMASK or DD_ACT_F32X3            */
+    int32_t drop_last;           /* nonzero: no tail minibatch                */
+    int64_t m;                   /* rows of one epoch                         */
+    int64_t epoch_stride;        /* rows from one epoch's batch to the next   */
+    int32_t num_epochs;
+    int32_t minibatch_size;
+    double clip_epsilon;
+    double entropy_coef;
+    double value_coef;
+    double max_grad_norm;        /* <= 0 or inf: no clipping                  */
+    double *logs;                /* [DD_PPO_FUSED_LOGS][num_epochs][steps]    */
+} DDPpoFusedIO;
+
+int64_t dd_ppo_update_fused_workspace(void);
+int dd_ppo_update_fused(const DDPpoFusedIO *io, void *workspace, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -23,6 +23,7 @@
 #include <stdint.h>
 
 #include "dronestep.h"
+#include "adamw_core.h"
 #include "launch.h"
 
 namespace dd {
@@ -30,19 +31,7 @@ namespace adamw {
 
 constexpr int kThreads = 1024;
 constexpr int kPer = 28;  // 28 x 1,024 = 28,672 >= 27,651 (the actor)
-
-// the fourteen tensors' first elements in the flat buffer (DDMlpParams' order)
-constexpr int oW0 = 0, oB0 = oW0 + 128 * 15, oG1 = oB0 + 128, oE1 = oG1 + 128;
-constexpr int oW3 = oE1 + 128, oB3 = oW3 + 128 * 128, oG4 = oB3 + 128, oE4 = oG4 + 128;
-constexpr int oW6 = oE4 + 128, oB6 = oW6 + 64 * 128, oG7 = oB6 + 64, oE7 = oG7 + 64;
-constexpr int oW9 = oE7 + 64;
-__host__ __device__ constexpr int params_of(int k) { return oW9 + 65 * k; }
 static_assert(params_of(3) == 27651 && params_of(1) == 27521 && params_of(3) <= kPer * kThreads, "flat layout");
-
-struct Args {
-    double lr, beta1, beta2, eps;
-    double decay, omb1, omb2;  // 1 - lr wd, 1 - beta1, 1 - beta2
-};
 
 // The f16x3 forward's operand ranges (delivery_drone_amd/policy.py _validated).
 constexpr float kWeightLimit = 65504.0f / 32;  // hidden weights: centred and x16 they must stay in f16
@@ -61,9 +50,7 @@ __global__ __launch_bounds__(kThreads) void step_kernel(float* __restrict__ p, c
     const int tid = threadIdx.x;
     const int64_t step = st->step;
     const int32_t status = st->status;
-    const double b1t = st->beta1_t * a.beta1, b2t = st->beta2_t * a.beta2;
-    const double step_size = a.lr / (1.0 - b1t);
-    const double root = sqrt(1.0 - b2t);
+    const Step now = step_of(a, st->beta1_t, st->beta2_t);
 
     float cp[kPer], cm[kPer], cv[kPer];
     float top[kMaxima] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
@@ -72,14 +59,7 @@ __global__ __launch_bounds__(kThreads) void step_kernel(float* __restrict__ p, c
         const int e = i * kThreads + tid;
         cp[i] = cm[i] = cv[i] = 0.0f;
         if (e < n) {
-            const double gd = (double)g[e];
-            const double pd = (double)p[e] * a.decay;
-            const double md = a.beta1 * (double)m[e] + a.omb1 * gd;
-            const double vd = a.beta2 * (double)v[e] + a.omb2 * (gd * gd);
-            const double pn = pd - step_size * (md / (sqrt(vd) / root + a.eps));
-            cp[i] = (float)pn;
-            cm[i] = (float)md;
-            cv[i] = (float)vd;
+            element(a, now, p[e], g[e], m[e], v[e], cp[i], cm[i], cv[i]);
             if constexpr (!kCheck) {  // nothing can refuse the step: each thread owns its elements
                 p[e] = cp[i];
                 m[e] = cm[i];
@@ -132,8 +112,8 @@ __global__ __launch_bounds__(kThreads) void step_kernel(float* __restrict__ p, c
         }
         if (tid == 0) {
             st->step = step + 1;
-            st->beta1_t = b1t;
-            st->beta2_t = b2t;
+            st->beta1_t = now.b1t;
+            st->beta2_t = now.b2t;
         }
     } else if (tid == 0) {
         st->status = status | DD_ADAMW_REFUSED;
@@ -155,8 +135,6 @@ __global__ __launch_bounds__(256) void init_kernel(float* __restrict__ m, float*
         st->_pad = 0;
     }
 }
-
-inline bool is_rate(double x) { return __builtin_isfinite(x) && x >= 0.0; }
 
 }  // namespace adamw
 }  // namespace dd
@@ -182,14 +160,11 @@ int dd_adamw_step(const DDAdamWHyper* hyper, const DDAdamWIO* io, void* stream) 
     if (reinterpret_cast<uintptr_t>(io->state) & 7u) return hipErrorInvalidValue;
     if (io->out_dim != 1 && io->out_dim != 3) return hipErrorInvalidValue;
     if (io->compute != DD_MLP_F32 && io->compute != DD_MLP_F16X3) return hipErrorInvalidValue;
-    if (!is_rate(hyper->lr) || !is_rate(hyper->eps) || !is_rate(hyper->weight_decay)) return hipErrorInvalidValue;
-    if (!is_rate(hyper->beta1) || !is_rate(hyper->beta2) || !(hyper->beta1 < 1.0) || !(hyper->beta2 < 1.0))
-        return hipErrorInvalidValue;
+    if (!hyper_ok(*hyper)) return hipErrorInvalidValue;
     if (io->packed && ((reinterpret_cast<uintptr_t>(io->packed) & 15u) || !(io->ln_eps > 0.0f)))
         return hipErrorInvalidValue;
     const int n = params_of(io->out_dim);
-    const Args a = {hyper->lr, hyper->beta1, hyper->beta2, hyper->eps, 1.0 - hyper->lr * hyper->weight_decay,
-                    1.0 - hyper->beta1, 1.0 - hyper->beta2};
+    const Args a = args_of(*hyper);
     hipStream_t s = static_cast<hipStream_t>(stream);
     dd::with_bool(io->compute == DD_MLP_F16X3, [&](auto check) {
         hipLaunchKernelGGL(step_kernel<decltype(check)::value>, dim3(1), dim3(kThreads), 0, s, io->params, io->grads,
@@ -197,9 +172,7 @@ int dd_adamw_step(const DDAdamWHyper* hyper, const DDAdamWIO* io, void* stream) 
     });
     const int e = dd::finish();
     if (e != 0 || !io->packed) return e;
-    float* q = io->params;
-    const DDMlpParams net = {q + oW0, q + oB0, q + oG1, q + oE1, q + oW3, q + oB3, q + oG4, q + oE4, q + oW6,
-                             q + oB6, q + oG7, q + oE7, q + oW9, q + oW9 + 64 * io->out_dim, io->out_dim, io->ln_eps};
+    const DDMlpParams net = params_view(io->params, io->out_dim, io->ln_eps);
     return dd_mlp_pack(&net, io->compute, io->packed, stream);
 }
 

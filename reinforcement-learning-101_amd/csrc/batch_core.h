@@ -38,6 +38,18 @@ __device__ __forceinline__ V block_sum(V v, V* sh) {
     return total;
 }
 
+// block_sum's tree over kBlock values held by ONE wave, four per lane (lane l:
+// the values of threads l, l + 64, l + 128 and l + 192 of the block it stands
+// for): the same additions in the same grouping, so the same bits, without a
+// barrier or LDS.  Lane 0 gets the result.
+__device__ __forceinline__ double wave_block_sum(const double (&x)[4]) {
+    static_assert(kBlock == 256, "four values per lane");
+    double s = (x[0] + x[2]) + (x[1] + x[3]);  // half = 128, then 64
+#pragma unroll
+    for (int half = 32; half > 0; half >>= 1) s += __shfl_down(s, half, 64);
+    return s;
+}
+
 // The batch's total from the kStatBlocks partials of a kStatBlocks-block
 // launch, the same tree in every block.  sh as block_sum's.
 template <typename V>

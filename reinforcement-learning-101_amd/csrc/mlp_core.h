@@ -77,6 +77,78 @@ constexpr bool kCentered = true;
 // (C/D map of the 32x32 MFMAs on gfx950: row = (r&3) + 8(r>>2) + 4h).
 __host__ __device__ constexpr int hid(int t, int r, int h) { return 32 * t + (r & 3) + 8 * (r >> 2) + 4 * h; }
 
+// ---- dd_mlp_pack's arithmetic ------------------------------------------------
+// The three hidden Linears' weights and biases are centred over their output
+// rows: w - (sum of the column's rows, in row order, in double) / rows, rounded
+// once.
+__device__ __forceinline__ double column_mean(const float* w, int rows, int cols, int col) {
+    double sum = 0.0;
+    for (int r = 0; r < rows; ++r) sum += (double)w[r * cols + col];
+    return sum / rows;
+}
+__device__ __forceinline__ float centred(float w, double mean) { return (float)((double)w - mean); }
+
+// DD_MLP_F32: the power of two that scales a LayerNorm's output (its weight
+// and bias are packed times it) so that every output stays below 1, which
+// makes ReLU the clamp modifier of the affine FMA (norm_relu_emit).  A
+// LayerNorm output is gamma * xn + beta with |xn| < sqrt(rows) (the normalised
+// column has mean square below 1), so |out| < B = max|gamma| sqrt(rows) (1 +
+// 2^-8, for rounding) + max|beta|; with B = m 2^x, m in [0.5, 1), the scale is
+// 2^-x.  The next LayerNorm removes it exactly (its eps is packed at the scale
+// squared).
+__device__ __forceinline__ float act_scale_of(const float* g, const float* b, int rows) {
+    float gm = 0.0f, bm = 0.0f;
+    for (int r = 0; r < rows; ++r) {
+        gm = fmaxf(gm, fabsf(g[r]));
+        bm = fmaxf(bm, fabsf(b[r]));
+    }
+    const float bound = gm * sqrtf((float)rows) * (1.0f + 0x1p-8f) + bm;
+    if (!(bound > 0.0f)) return 1.0f;
+    int x;
+    frexpf(bound, &x);
+    return ldexpf(1.0f, -x);
+}
+
+// Float i of the DD_MLP_F32 packed buffer.  t answers what many elements
+// share: t.weight_mean(base, col) and t.bias_mean(L), the column means of the
+// hidden Linear at section base (kA1, kA2, kA3) and of the bias before
+// LayerNorm L, and t.act_scale(L).
+template <typename Table>
+__device__ __forceinline__ float pack_f32_at(const DDMlpParams& p, int i, const Table& t) {
+    static_assert(kCentered, "the hidden Linears are packed centred");
+    if (i < kV1) {  // A operands: lane l of k-step q of out tile t holds W[32t + (l&31)][k(q, l>>5)]
+        const int base = i < kA2 ? kA1 : i < kA3 ? kA2 : kA3;
+        const int steps = i < kA2 ? kSteps1 : i < kA3 ? kSteps2 : kSteps3;
+        const int o = i - base;
+        const int j = o & 3, l = (o >> 2) & 63, grp = o >> 8;
+        const int tile = grp / (steps / 4), q = 4 * (grp % (steps / 4)) + j;
+        const int row = 32 * tile + (l & 31), h = l >> 5;
+        // layer 1: natural k order, column 15 is zero; layers 2, 3: k-step
+        // (t', r) = q takes hidden row hid(t', r, h)
+        const int col = base == kA1 ? 2 * q + h : hid(q >> 4, q & 15, h);
+        if (base == kA1 && col >= kIn) return 0.0f;
+        const float* w = base == kA1 ? p.w0 : base == kA2 ? p.w3 : p.w6;
+        return centred(w[row * (base == kA1 ? kIn : 128) + col], t.weight_mean(base, col));
+    }
+    if (i < kW4) {  // [bias | LN weight | LN bias] of layers 1-3
+        const int L = i < kV2 ? 0 : i < kV3 ? 1 : 2, rows = L == 2 ? 64 : 128;
+        const int o = i - (L == 0 ? kV1 : L == 1 ? kV2 : kV3);
+        const float* src[3][3] = {{p.b0, p.ln1_w, p.ln1_b}, {p.b3, p.ln4_w, p.ln4_b}, {p.b6, p.ln7_w, p.ln7_b}};
+        // the bias at its GEMM's scale (the input's); the LN's affine at its output's
+        if (o < rows) return centred(src[L][0][o], t.bias_mean(L)) * (L == 0 ? 1.0f : t.act_scale(L - 1));
+        return src[L][o / rows][o % rows] * t.act_scale(L);
+    }
+    if (i < kB4) {  // the last layer: the last LayerNorm's output is scaled
+        const int o = i - kW4;
+        return ((o / 64) < p.out_dim ? p.w9[o] : 0.0f) * (1.0f / t.act_scale(2));
+    }
+    if (i == kFold) return 0.0f;
+    if (i < kTag) return i - kB4 < p.out_dim ? p.b9[i - kB4] : 0.0f;
+    if (i == kTag) return __uint_as_float(pack_tag(DD_MLP_F32, p.out_dim));
+    const float sc = i == kEps ? 1.0f : t.act_scale(i - kEps - 1);  // kEps: each LayerNorm's eps at its input's scale squared
+    return p.ln_eps * sc * sc;
+}
+
 // ---- DD_MLP_F16X3: split operands on the f16 MFMA --------------------------
 // Every operand is split a = hi + lo, hi = f16(a), lo = f16(a - hi), both
 // rounded to nearest-even (a - hi is exact in f32), and a product is

@@ -61,17 +61,13 @@ __device__ __forceinline__ float weight_at(const DDMlpParams& p, int base, int r
     const float* w = base == kA1 ? p.w0 : base == kA2 ? p.w3 : p.w6;
     const int cols = base == kA1 ? kIn : 128, rows = base == kA3 ? 64 : 128;
     if (!kCentered) return w[row * cols + col];
-    double sum = 0.0;
-    for (int r = 0; r < rows; ++r) sum += (double)w[r * cols + col];
-    return (float)((double)w[row * cols + col] - sum / rows);
+    return centred(w[row * cols + col], column_mean(w, rows, cols, col));
 }
 
 // A Linear bias before a LayerNorm, centred like its weights.
 __device__ __forceinline__ float bias_at(const float* b, int rows, int o) {
     if (!kCentered) return b[o];
-    double sum = 0.0;
-    for (int r = 0; r < rows; ++r) sum += (double)b[r];
-    return (float)((double)b[o] - sum / rows);
+    return centred(b[o], column_mean(b, rows, 1, 0));
 }
 
 // ---- DD_MLP_F16X3: LayerNorm weights folded into the next layer ----------
@@ -176,66 +172,49 @@ __device__ __forceinline__ float pack_a16(const DDMlpParams& p, const float* out
     return __uint_as_float(part == 0 ? hi : lo);
 }
 
-// DD_MLP_F32: the power of two that scales LayerNorm L's output (its weight
-// and bias are packed times it) so that every output stays below 1, which
-// makes ReLU the clamp modifier of the affine FMA (mlp_core.h norm_relu_emit).
-// A LayerNorm output is gamma * xn + beta with |xn| < sqrt(rows) (the
-// normalised column has mean square below 1), so |out| < B = max|gamma|
-// sqrt(rows) (1 + 2^-8, for rounding) + max|beta|; with B = m 2^x, m in [0.5,
-// 1), the scale is 2^-x.  The next LayerNorm removes it exactly (its eps is
-// packed at the scale squared).
-__device__ __forceinline__ float act_scale(const DDMlpParams& p, int L) {
-    const float* g = L == 0 ? p.ln1_w : L == 1 ? p.ln4_w : p.ln7_w;
-    const float* b = L == 0 ? p.ln1_b : L == 1 ? p.ln4_b : p.ln7_b;
-    const int rows = L == 2 ? 64 : 128;
-    float gm = 0.0f, bm = 0.0f;
-    for (int r = 0; r < rows; ++r) {
-        gm = fmaxf(gm, fabsf(g[r]));
-        bm = fmaxf(bm, fabsf(b[r]));
+// DD_MLP_F32's packed floats (mlp_core.h pack_f32_at), every shared quantity
+// computed where it is asked for.
+struct PackDirect {
+    const DDMlpParams& p;
+    __device__ double weight_mean(int base, int col) const {
+        return base == kA1 ? column_mean(p.w0, 128, kIn, col)
+                           : base == kA2 ? column_mean(p.w3, 128, 128, col) : column_mean(p.w6, 64, 128, col);
     }
-    const float bound = gm * sqrtf((float)rows) * (1.0f + 0x1p-8f) + bm;
-    if (!(bound > 0.0f)) return 1.0f;
-    int x;
-    frexpf(bound, &x);
-    return ldexpf(1.0f, -x);
-}
+    __device__ double bias_mean(int L) const {
+        return L == 0 ? column_mean(p.b0, 128, 1, 0) : L == 1 ? column_mean(p.b3, 128, 1, 0) : column_mean(p.b6, 64, 1, 0);
+    }
+    __device__ float act_scale(int L) const {
+        return L == 0 ? act_scale_of(p.ln1_w, p.ln1_b, 128)
+                      : L == 1 ? act_scale_of(p.ln4_w, p.ln4_b, 128) : act_scale_of(p.ln7_w, p.ln7_b, 64);
+    }
+};
 
 // One packed float: which state_dict element (or zero) goes at index i.
 __global__ void pack_kernel(DDMlpParams p, int32_t compute, float* out) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= kPacked) return;
-    const bool split = compute == DD_MLP_F16X3;
+    if (compute != DD_MLP_F16X3) {
+        out[i] = pack_f32_at(p, i, PackDirect{p});
+        return;
+    }
     float v = 0.0f;
-    if (i < kV1 && compute == DD_MLP_F16X3) {
+    if (i < kV1) {
         v = pack_a16(p, out, i);
-    } else if (i < kV1) {  // A operands: lane l of k-step q of out tile t holds W[32t + (l&31)][k(q, l>>5)]
-        const int base = i < kA2 ? kA1 : i < kA3 ? kA2 : kA3;
-        const int steps = i < kA2 ? kSteps1 : i < kA3 ? kSteps2 : kSteps3;
-        const int o = i - base;
-        const int j = o & 3, l = (o >> 2) & 63, grp = o >> 8;
-        const int t = grp / (steps / 4), q = 4 * (grp % (steps / 4)) + j;
-        const int row = 32 * t + (l & 31), h = l >> 5;
-        // layer 1: natural k order, column 15 is zero; layers 2, 3: k-step
-        // (t', r) = q takes hidden row hid(t', r, h)
-        const int col = base == kA1 ? 2 * q + h : hid(q >> 4, q & 15, h);
-        v = weight_at(p, base, row, col);
     } else if (i < kW4) {  // [bias | LN weight | LN bias] of layers 1-3
         const int L = i < kV2 ? 0 : i < kV3 ? 1 : 2, rows = L == 2 ? 64 : 128;
         const int o = i - (L == 0 ? kV1 : L == 1 ? kV2 : kV3);
         const float* src[3][3] = {{p.b0, p.ln1_w, p.ln1_b}, {p.b3, p.ln4_w, p.ln4_b}, {p.b6, p.ln7_w, p.ln7_b}};
         v = o < rows ? bias_at(src[L][0], rows, o) : src[L][o / rows][o % rows];
-        if (split && o < rows) v *= row_sign(p, out, L, o);                       // folded: the row's sign
-        if (split && o >= 2 * rows && folded(out, L)) v /= fabsf(src[L][1][o % rows]);  // beta / |gamma|
+        if (o < rows) v *= row_sign(p, out, L, o);                                // folded: the row's sign
+        if (o >= 2 * rows && folded(out, L)) v /= fabsf(src[L][1][o % rows]);  // beta / |gamma|
         // the bias at its GEMM's scale (weights x input); the LN's affine at its output's
-        const float in = L == 0 ? (split ? kInScale : 1.0f) : split ? kActScale : act_scale(p, L - 1);
-        v *= o < rows ? (split ? kWScale : 1.0f) * in : split ? kActScale : act_scale(p, L);
+        v *= o < rows ? kWScale * (L == 0 ? kInScale : kActScale) : kActScale;
     } else if (i < kB4) {
         const int o = i - kW4;
         v = (o / 64) < p.out_dim ? p.w9[o] : 0.0f;
-        if (split) v *= col_gain(p, out, 2, o % 64);
-        v *= 1.0f / (split ? kActScale : act_scale(p, 2));  // the last LayerNorm's output is scaled
-    } else if (i == kFold) {  // fold_kernel's flags (DD_MLP_F16X3), none for f32
-        if (!split) out[i] = 0.0f;
+        v *= col_gain(p, out, 2, o % 64);
+        v *= 1.0f / kActScale;  // the last LayerNorm's output is scaled
+    } else if (i == kFold) {  // fold_kernel's flags
         return;
     } else if (i < kTag) {
         const int o = i - kB4;
@@ -243,8 +222,7 @@ __global__ void pack_kernel(DDMlpParams p, int32_t compute, float* out) {
     } else if (i == kTag) {
         v = __uint_as_float(pack_tag(compute, p.out_dim));
     } else {  // kEps: each LayerNorm's eps at its input's scale squared
-        const float sc = split ? kWScale * (i == kEps ? kInScale : kActScale)
-                               : (i == kEps ? 1.0f : act_scale(p, i - kEps - 1));
+        const float sc = kWScale * (i == kEps ? kInScale : kActScale);
         v = p.ln_eps * sc * sc;
     }
     out[i] = v;

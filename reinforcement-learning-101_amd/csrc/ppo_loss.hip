@@ -65,59 +65,29 @@
 #include "batch_core.h"
 #include "dronestep.h"
 #include "launch.h"
+#include "ppo_core.h"
 
 namespace dd {
 namespace ppo {
 
-// One thread's, block's or the batch's sums; += is the tree's node.  min and
-// max carry a NaN ratio on, as torch.min / torch.max do.
-struct Part {
-    double surr, sq, ent, r, clipped;
-    float rmin, rmax;
-    __device__ __forceinline__ Part& operator+=(const Part& b) {
-        surr += b.surr;
-        sq += b.sq;
-        ent += b.ent;
-        r += b.r;
-        clipped += b.clipped;
-        rmin = (b.rmin < rmin || b.rmin != b.rmin) ? b.rmin : rmin;
-        rmax = (b.rmax > rmax || b.rmax != b.rmax) ? b.rmax : rmax;
-        return *this;
-    }
-};
-
-__device__ __forceinline__ float ratio_of(float lp, float old) { return (float)exp((double)(lp - old)); }
-
 __global__ __launch_bounds__(kBlock) void ppo_rows_kernel(DDPpoLossIO io, int64_t m, float lo, float hi,
                                                           Part* __restrict__ part) {
     __shared__ Part sh[kBlock];
-    Part acc = {0.0, 0.0, 0.0, 0.0, 0.0, INFINITY, -INFINITY};
+    Part acc = no_rows();
     const double md = (double)m;
     for (int64_t k = (int64_t)blockIdx.x * kBlock + threadIdx.x; k < m; k += (int64_t)kStatBlocks * kBlock) {
-        const float rf = ratio_of(io.log_prob[k], io.old_log_prob[k]);
-        const float cf = rf < lo ? lo : rf > hi ? hi : rf;  // torch.clamp: a NaN stays
-        const bool outside = rf < lo || rf > hi;
-        const double r = rf, A = io.advantages[k];
-        const double s1 = r * A, s2 = (double)cf * A;
+        const Surrogate s = surrogate_of(io.log_prob[k], io.old_log_prob[k], io.advantages[k], lo, hi);
         const double dv = (double)io.values[k] - (double)io.returns[k];
-        Part row = {s2 < s1 ? s2 : s1, dv * dv, (double)io.entropy[k], r, outside ? 1.0 : 0.0, rf, rf};
+        Part row = {s.smaller(), dv * dv, (double)io.entropy[k], s.r, s.outside ? 1.0 : 0.0, s.rf, s.rf};
         acc += row;
-        if (io.ratio) io.ratio[k] = rf;
-        if (io.grad_values) io.grad_values[k] = (float)(io.value_coef * 2.0 * dv / md);
+        if (io.ratio) io.ratio[k] = s.rf;
+        if (io.grad_values) io.grad_values[k] = grad_value_of(io.value_coef, dv, md);
         if (io.grad_logits) {
-            // the clipped branch taken (or tied with A == 0) outside the range: no gradient
-            const double g = !(s1 < s2) && outside ? 0.0 : -A * r / md;
+            const double g = s.grad(md);
             const uint32_t bits = given_bits(io.actions, io.action_format, k);
 #pragma unroll
-            for (int j = 0; j < 3; ++j) {
-                const float pf = io.probs[k * 3 + j];
-                double v = pf != pf ? (double)pf : 0.0;  // outside clamp_probs' range: 0 (NaN stays)
-                if (pf >= FLT_EPSILON && pf <= 1.0f - FLT_EPSILON) {
-                    const double p = pf, a = (double)((bits >> j) & 1u);
-                    v = g * (a - p) + io.entropy_coef / (3.0 * md) * (log(p) - log1p(-p)) * (p * (1.0 - p));
-                }
-                io.grad_logits[k * 3 + j] = (float)v;
-            }
+            for (int j = 0; j < 3; ++j)
+                io.grad_logits[k * 3 + j] = grad_logit_of(g, (bits >> j) & 1u, io.probs[k * 3 + j], io.entropy_coef, md);
         }
     }
     acc = block_sum<Part>(acc, sh);
@@ -150,15 +120,15 @@ __global__ __launch_bounds__(kBlock) void ppo_finish_kernel(const Part* __restri
     const double ss = stat_total(part_ss, shd);
     if (threadIdx.x != 0) return;
     const double md = (double)m;
-    const double policy = -(t.surr / md), value = t.sq / md, entropy = t.ent / (3.0 * md);
-    result[DD_PPO_TOTAL_LOSS] = policy + value_coef * value - entropy_coef * entropy;
+    const double policy = policy_loss_of(t, md), value = value_loss_of(t.sq, md), entropy = entropy_of(t, md);
+    result[DD_PPO_TOTAL_LOSS] = total_loss_of(policy, value, entropy, entropy_coef, value_coef);
     result[DD_PPO_POLICY_LOSS] = policy;
     result[DD_PPO_VALUE_LOSS] = value;
     result[DD_PPO_ENTROPY] = entropy;
     result[DD_PPO_RATIO_MEAN] = t.r / md;
     result[DD_PPO_RATIO_MIN] = (double)t.rmin;
     result[DD_PPO_RATIO_MAX] = (double)t.rmax;
-    result[DD_PPO_RATIO_STD] = m < 2 ? __builtin_nan("") : sqrt(ss / (double)(m - 1));  // torch.std's default: unbiased
+    result[DD_PPO_RATIO_STD] = ratio_std_of(ss, m);
     result[DD_PPO_CLIPPED_FRAC] = t.clipped / md;
 }
 

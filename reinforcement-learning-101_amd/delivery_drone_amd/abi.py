@@ -27,7 +27,8 @@ __all__ = [
     "DD_ADAMW_REFUSED", "DDAdamWHyper", "DDAdamWState", "DDAdamWIO",
     "DD_PG_LOSS", "DD_PG_COUNT", "DD_PG_RESULTS", "DDPgLossIO",
     "DD_TD_CRITIC_LOSS", "DD_TD_MSE", "DD_TD_VALUE_REG", "DD_TD_COUNT", "DD_TD_RESULTS", "DDTdLossIO",
-    "DDShuffleIO", "DD_REWARD_PARTS", "DDRewardParts", "REWARD_PART_NAMES",
+    "DDShuffleIO", "DD_PPO_FUSED_ROWS", "DD_PPO_POLICY_GRAD_NORM", "DD_PPO_CRITIC_GRAD_NORM", "DD_PPO_FUSED_LOGS",
+    "DDPpoFusedNet", "DDPpoFusedIO", "DD_REWARD_PARTS", "DDRewardParts", "REWARD_PART_NAMES",
     "sampling_mode", "lib", "load", "library_path", "check",
     "NativeLibraryError",
 ]
@@ -60,6 +61,8 @@ DD_EPISODES_DROP_OPEN = 1
  DD_PPO_RATIO_MAX, DD_PPO_RATIO_STD, DD_PPO_CLIPPED_FRAC, DD_PPO_RESULTS) = range(10)
 
 DD_ADAMW_REFUSED = 1
+DD_PPO_FUSED_ROWS = 128
+DD_PPO_POLICY_GRAD_NORM, DD_PPO_CRITIC_GRAD_NORM, DD_PPO_FUSED_LOGS = 9, 10, 11
 DD_PG_LOSS, DD_PG_COUNT, DD_PG_RESULTS = range(3)
 DD_TD_CRITIC_LOSS, DD_TD_MSE, DD_TD_VALUE_REG, DD_TD_COUNT, DD_TD_RESULTS = range(5)
 
@@ -252,6 +255,23 @@ class DDShuffleIO(ctypes.Structure):
                 ("returns_out", ctypes.c_void_p), ("indices", ctypes.c_void_p)]
 
 
+class DDPpoFusedNet(ctypes.Structure):
+    """One network of ``dd_ppo_update_fused``: its flat buffers, state block,
+    packed image and optimizer settings."""
+
+    _fields_ = [("params", ctypes.c_void_p), ("grads", ctypes.c_void_p), ("exp_avg", ctypes.c_void_p),
+                ("exp_avg_sq", ctypes.c_void_p), ("state", ctypes.c_void_p), ("packed", ctypes.c_void_p),
+                ("hyper", DDAdamWHyper), ("ln_eps", ctypes.c_float), ("_pad", _I)]
+
+
+class DDPpoFusedIO(ctypes.Structure):
+    _fields_ = [("actor", DDPpoFusedNet), ("critic", DDPpoFusedNet), ("states", ctypes.c_void_p),
+                ("actions", ctypes.c_void_p), ("old_log_probs", ctypes.c_void_p), ("advantages", ctypes.c_void_p),
+                ("returns", ctypes.c_void_p), ("action_format", _I), ("drop_last", _I), ("m", ctypes.c_int64),
+                ("epoch_stride", ctypes.c_int64), ("num_epochs", _I), ("minibatch_size", _I), ("clip_epsilon", _D),
+                ("entropy_coef", _D), ("value_coef", _D), ("max_grad_norm", _D), ("logs", ctypes.c_void_p)]
+
+
 def sampling_mode(temperature) -> int:
     """The ``DD_SAMPLE_*`` mode of a notebook ``temperature``: 1 is the plain
     Bernoulli draw, 0 greedy (``probs > 0.5``), any other positive finite value
@@ -365,6 +385,8 @@ EXPORTS = {
                                           ctypes.c_void_p]),
     "dd_shuffle_rows": (ctypes.c_int, [ctypes.POINTER(DDShuffleIO), ctypes.c_int64, ctypes.c_uint64, ctypes.c_uint64,
                                        ctypes.c_void_p]),
+    "dd_ppo_update_fused_workspace": (ctypes.c_int64, []),
+    "dd_ppo_update_fused": (ctypes.c_int, [ctypes.POINTER(DDPpoFusedIO), ctypes.c_void_p, ctypes.c_void_p]),
 }
 
 #: symbols a timing-only lab build (tools/build_variants.sh) or an older
@@ -377,7 +399,8 @@ _LAB_OPTIONAL = ("dd_build_info", "dd_selftest_sqrt", "dd_rollout_kernel", "dd_s
                  "dd_ppo_loss_workspace", "dd_ppo_losses", "dd_mlp_backward_workspace", "dd_mlp_backward",
                  "dd_adamw_state_bytes", "dd_adamw_init", "dd_adamw_step", "dd_pg_loss_workspace", "dd_pg_losses",
                  "dd_td_loss_workspace", "dd_td_losses", "dd_shuffle_indices", "dd_shuffle_rows",
-                 "dd_policy_evaluate_parts", "dd_policy_rollout_population", "dd_render_grid")
+                 "dd_policy_evaluate_parts", "dd_policy_rollout_population", "dd_render_grid",
+                 "dd_ppo_update_fused_workspace", "dd_ppo_update_fused")
 
 
 class NativeLibraryError(RuntimeError):

@@ -25,10 +25,10 @@ import torch
 from . import abi
 from .policy import STATE_DICT_KEYS, MlpNet
 from .ppo_loss import ppo_losses
-from .shuffle import shuffle_batch
+from .shuffle import ShuffledBatch, _column, shuffle_batch
 from .train_batch import PpoBatch, PpoEpisodesBatch
 
-__all__ = ["AdamW", "PpoUpdate", "ppo_update"]
+__all__ = ["AdamW", "PpoUpdate", "ppo_update", "fused_rows", "fits_fused", "FUSED_MAX_ROWS"]
 
 _STATE = struct.Struct("<qddii")  # DDAdamWState
 
@@ -225,10 +225,104 @@ def minibatch_ranges(m: int, size: int, drop_last: bool = False):
     return [(lo, min(lo + size, m)) for lo in range(0, stop, size)]
 
 
+#: the largest minibatch ``ppo_update(fused=True)`` takes: ``dd_mlp_backward``'s row tile
+FUSED_MAX_ROWS = abi.DD_PPO_FUSED_ROWS
+
+
+def fused_rows(m: int, minibatch_size: Optional[int] = None, drop_last: bool = False) -> int:
+    """The rows of the largest step ``ppo_update(minibatch_size=...,
+    drop_last=...)`` takes on a batch of ``m`` rows: ``m`` itself for the full
+    batch, else the longest of :func:`minibatch_ranges` (0 when there is none)."""
+    if minibatch_size is None:
+        return int(m)
+    return max((hi - lo for lo, hi in minibatch_ranges(int(m), int(minibatch_size), drop_last)), default=0)
+
+
+def fits_fused(m: int, minibatch_size: Optional[int] = None, drop_last: bool = False) -> bool:
+    """Whether every step of such an update is at most one row tile
+    (``FUSED_MAX_ROWS`` rows), which is what ``fused=True`` needs."""
+    return 1 <= fused_rows(m, minibatch_size, drop_last) <= FUSED_MAX_ROWS
+
+
+def _fused_net(net: MlpNet, opt: "AdamW") -> abi.DDPpoFusedNet:
+    hyper = abi.DDAdamWHyper(opt._lr, opt.betas[0], opt.betas[1], opt.eps, opt.weight_decay)
+    return abi.DDPpoFusedNet(opt.params.data_ptr(), opt._grad_out.data_ptr(), opt.exp_avg.data_ptr(),
+                             opt.exp_avg_sq.data_ptr(), opt._state.data_ptr(), net.packed.data_ptr(), hyper,
+                             net.ln_eps, 0)
+
+
+def _ppo_update_fused(actor, critic, five, actor_opt, critic_opt, num_epochs, clip_epsilon, entropy_coef, value_coef,
+                      max_grad_norm, minibatch_size, shuffle_seed, shuffle_epoch, drop_last) -> torch.Tensor:
+    """``ppo_update``'s loop as ``dd_ppo_update_fused``: the ``[11, num_epochs,
+    steps]`` log tensor.  The argument checks of the loop it replaces, in
+    their order, then its own two limits."""
+    size = None if minibatch_size is None else int(minibatch_size)
+    if size is not None and size < 1:
+        raise ValueError(f"minibatch_size must be at least 1, got {minibatch_size!r}")
+    if len(five) == 1:  # a batch: its five tensors
+        if not isinstance(five[0], (PpoBatch, PpoEpisodesBatch)):
+            raise ValueError("batch must be a PpoBatch, a PpoEpisodesBatch or the five tensors")
+        five = tuple(five[0][:5])
+    if len(five) != 5 or not all(isinstance(t, torch.Tensor) for t in five):
+        raise ValueError("fused=True needs all five tensors (states, actions, old_log_probs, advantages, returns)")
+    m = int(five[0].shape[0])
+    steps = 1 if size is None else len(minibatch_ranges(m, size, drop_last))
+    if steps == 0:
+        raise ValueError(f"no minibatch to step on: {m} rows, minibatch_size {size}, drop_last={bool(drop_last)}")
+    if m == 0:
+        raise ValueError("ppo_losses needs at least one row: a mean over no rows has no value")
+    if getattr(actor, "out_dim", None) != 3 or getattr(critic, "out_dim", None) != 1:
+        raise ValueError("ppo_losses needs an MlpNet actor (out_dim 3) and an MlpNet critic (out_dim 1)")
+    if critic.device != actor.device:
+        raise ValueError(f"the actor is on {actor.device}, the critic on {critic.device}")
+    for name, c in (("clip_epsilon", clip_epsilon), ("entropy_coef", entropy_coef), ("value_coef", value_coef)):
+        if not math.isfinite(float(c)):
+            raise ValueError(f"{name} must be finite, got {c!r}")
+    if float(clip_epsilon) < 0.0:
+        raise ValueError(f"clip_epsilon must not be negative, got {clip_epsilon!r}")
+    if max_grad_norm is not None and math.isnan(float(max_grad_norm)):
+        raise ValueError("max_norm must not be NaN")
+    for name, net in (("actor", actor), ("critic", critic)):
+        if net.compute != "f32":
+            raise ValueError(f"fused=True runs compute='f32' networks only, the {name} is compute={net.compute!r}; "
+                             "use fused=False")
+    rows = fused_rows(m, size, drop_last)
+    if rows > FUSED_MAX_ROWS:
+        raise ValueError(f"fused=True takes minibatches of at most {FUSED_MAX_ROWS} rows (one row tile of the "
+                         f"backward), this update has one of {rows}; pass minibatch_size <= {FUSED_MAX_ROWS} or "
+                         "fused=False")
+    dev = actor.device
+    if five[0].dim() != 2 or five[0].shape[1] != abi.DD_OBS_DIM:
+        raise ValueError(f"states must be [M, {abi.DD_OBS_DIM}]")
+    cols = [_column(name, t, m, dev) for name, t in zip(ShuffledBatch._fields[:5], five)]
+    stride = 0
+    if size is not None:  # the epochs' shuffled batches, one after the other: num_epochs launches, whatever M / B is
+        stacked = [torch.empty((num_epochs * m,) + tuple(c.shape[1:]), dtype=c.dtype, device=dev) for c in cols]
+        indices = torch.empty(m, dtype=torch.int32, device=dev)
+        for epoch in range(num_epochs):
+            out = ShuffledBatch(*(t[epoch * m:(epoch + 1) * m] for t in stacked), indices)
+            shuffle_batch(cols, seed=shuffle_seed, epoch=int(shuffle_epoch) + epoch, out=out)
+        cols, stride = stacked, m
+    lib = actor._lib
+    ws = getattr(actor_opt, "_fused_ws", None)
+    if ws is None:  # the backward's weight images and head gradients of both networks: a fixed size, kept
+        ws = actor_opt._fused_ws = torch.empty(int(lib.dd_ppo_update_fused_workspace()) // 8, dtype=torch.int64,
+                                               device=dev)
+    logs = torch.empty(abi.DD_PPO_FUSED_LOGS, num_epochs, steps, dtype=torch.float64, device=dev)
+    fmt = abi.DD_ACT_BITMASK if cols[1].dtype == torch.uint8 else abi.DD_ACT_F32X3
+    io = abi.DDPpoFusedIO(_fused_net(actor, actor_opt), _fused_net(critic, critic_opt), cols[0].data_ptr(),
+                          cols[1].data_ptr(), cols[2].data_ptr(), cols[3].data_ptr(), cols[4].data_ptr(), fmt,
+                          1 if drop_last else 0, m, stride, num_epochs, min(size, m) if size is not None else m,
+                          float(clip_epsilon), float(entropy_coef), float(value_coef),
+                          float(max_grad_norm) if max_grad_norm is not None else 0.0, logs.data_ptr())
+    abi.check(lib.dd_ppo_update_fused(ctypes.byref(io), ws.data_ptr(), actor._stream()), "dd_ppo_update_fused")
+    return logs
+
+
 def ppo_update(actor: MlpNet, critic: MlpNet, batch, actor_opt: AdamW, critic_opt: AdamW, *, num_epochs: int = 4,
                clip_epsilon: float = 0.2, entropy_coef: float = 0.01, value_coef: float = 0.5,
                max_grad_norm: float = 0.5, minibatch_size: Optional[int] = None, shuffle_seed: int = 0,
-               shuffle_epoch: int = 0, drop_last: bool = False) -> PpoUpdate:
+               shuffle_epoch: int = 0, drop_last: bool = False, fused: bool = False) -> PpoUpdate:
     """PHASE 3 of the notebook's training cell: ``num_epochs`` times
     ``compute_ppo_losses``, ``total_loss.backward()``, the two
     ``clip_grad_norm_`` and the two optimizer steps, on the full batch (a
@@ -251,6 +345,16 @@ def ppo_update(actor: MlpNet, critic: MlpNet, batch, actor_opt: AdamW, critic_op
     (for instance ``update * num_epochs``) or every call repeats the same
     permutations, and a captured graph replays the permutations it was
     captured with.
+
+    ``fused=True`` runs the same steps as one persistent launch
+    (``dd_ppo_update_fused``, ``csrc/ppo_fused.hip``: one workgroup per network
+    walks the epochs' minibatches in order) instead of about twenty launches
+    per step: the same logs, parameters, moments, state blocks and packed
+    images, bit for bit.  It needs ``compute="f32"`` networks and steps of at
+    most ``FUSED_MAX_ROWS`` = 128 rows (:func:`fits_fused`:
+    ``minibatch_size <= 128``, or a full batch of at most 128 rows) and raises
+    ``ValueError`` otherwise; the epochs' shuffled batches are laid out first,
+    one ``shuffle_batch`` launch per epoch.
 
     ``summary``: the steps' mean of every log under its own name (the cell's
     ``avg_*``: ``total_loss``, ..., ``ratio_mean``, ``ratio_std``,
@@ -285,7 +389,12 @@ def ppo_update(actor: MlpNet, critic: MlpNet, batch, actor_opt: AdamW, critic_op
         return torch.stack([losses.total_loss, losses.policy_loss, losses.value_loss, losses.entropy,
                             s["mean"], s["min"], s["max"], s["std"], s["clipped_frac"], n_actor, n_critic])
 
-    if minibatch_size is None:
+    if fused:
+        logs = _ppo_update_fused(actor, critic, five, actor_opt, critic_opt, num_epochs, clip_epsilon, entropy_coef,
+                                 value_coef, max_grad_norm, minibatch_size, shuffle_seed, shuffle_epoch, drop_last)
+        if minibatch_size is None:
+            logs = logs.view(len(LOG_KEYS), num_epochs)
+    elif minibatch_size is None:
         logs = torch.empty(len(LOG_KEYS), num_epochs, dtype=torch.float64, device=dev)
         for epoch in range(num_epochs):
             logs[:, epoch] = step(five)
