@@ -10,7 +10,10 @@ fail, writes nothing but a status bit.  :func:`ppo_update` is the training
 cell's ``for epoch in range(num_epochs)`` loop: :func:`ppo_losses`,
 :meth:`MlpNet.backward` and the two optimizer steps per epoch, with the
 per-epoch logs left on the device.  Nothing here reads back to the host
-unless asked (:meth:`AdamW.status`).
+unless asked (:meth:`AdamW.status`).  What an update accepts is stated once,
+by :func:`_plan` from the checks of ``_args``, for the loop and for
+``fused=True``; an :class:`AdamW` owns the gradient buffer every update
+function steps it from (:meth:`AdamW.grad_buffer`).
 """
 from __future__ import annotations
 
@@ -22,11 +25,10 @@ from typing import Dict, Mapping, NamedTuple, Optional, Union
 
 import torch
 
-from . import abi
+from . import _args, abi
 from .policy import STATE_DICT_KEYS, MlpNet
 from .ppo_loss import ppo_losses
-from .shuffle import ShuffledBatch, _column, shuffle_batch
-from .train_batch import PpoBatch, PpoEpisodesBatch
+from .shuffle import ShuffledBatch, shuffle_batch
 
 __all__ = ["AdamW", "PpoUpdate", "ppo_update", "fused_rows", "fits_fused", "FUSED_MAX_ROWS"]
 
@@ -61,6 +63,10 @@ class AdamW:
         self.exp_avg = torch.empty_like(self.params)
         self.exp_avg_sq = torch.empty_like(self.params)
         self._state = torch.empty(_STATE.size // 8, dtype=torch.int64, device=net.device)
+        self._grad_out = None  # grad_buffer(): the flat gradient the update functions fill and step from
+        # ppo_update(fused=True), on the actor's optimizer only: both networks' weight images and head
+        # gradients; dd_ppo_update_fused_workspace() bytes
+        self._fused_ws = None
         abi.check(self._lib.dd_adamw_init(self.exp_avg.data_ptr(), self.exp_avg_sq.data_ptr(), self.params.numel(),
                                           self._state.data_ptr(), net._stream()), "dd_adamw_init")
 
@@ -78,6 +84,16 @@ class AdamW:
     @lr.setter
     def lr(self, value) -> None:
         self._lr = self._rate("lr", value)
+
+    def grad_buffer(self) -> torch.Tensor:
+        """The optimizer's flat gradient buffer (``params``' shape), allocated
+        on first use and the same tensor from then on: ``backward``'s ``out``."""
+        if self._grad_out is None:
+            self._grad_out = torch.empty_like(self.params)
+        return self._grad_out
+
+    def _hyper(self) -> abi.DDAdamWHyper:
+        return abi.DDAdamWHyper(self._lr, self.betas[0], self.betas[1], self.eps, self.weight_decay)
 
     def step(self, grads: Union[torch.Tensor, Mapping[str, torch.Tensor]]) -> None:
         """One optimizer step from ``grads``: the flat gradient buffer, or the
@@ -100,7 +116,7 @@ class AdamW:
         if (tuple(flat.shape) != (self.params.numel(),) or flat.dtype != torch.float32 or not flat.is_contiguous()):
             raise ValueError(f"grads must be a contiguous float32 tensor of shape ({self.params.numel()},), got "
                              f"{flat.dtype} {tuple(flat.shape)}")
-        hyper = abi.DDAdamWHyper(self._lr, self.betas[0], self.betas[1], self.eps, self.weight_decay)
+        hyper = self._hyper()
         io = abi.DDAdamWIO(self.params.data_ptr(), flat.data_ptr(), self.exp_avg.data_ptr(),
                            self.exp_avg_sq.data_ptr(), self._state.data_ptr(), net.packed.data_ptr(), net.out_dim,
                            net._mode, net.ln_eps, 0)
@@ -129,14 +145,6 @@ class AdamW:
                              "dropped; the parameters of the last good step are in place; use compute='f32'")
 
     # ---- torch's optimizer-state layout ------------------------------------------------
-    def _views(self, flat: torch.Tensor) -> Dict[str, torch.Tensor]:
-        out, first = {}, 0
-        for k in STATE_DICT_KEYS:
-            n = self.net._src[k].numel()
-            out[k] = flat[first:first + n].view(self.net._src[k].shape)
-            first += n
-        return out
-
     def state_dict(self) -> dict:
         """``torch.optim.AdamW(...).state_dict()`` for the fourteen parameters
         in ``STATE_DICT_KEYS`` order (``network.parameters()``' order): per
@@ -149,7 +157,7 @@ class AdamW:
         step = self.step_count()
         state = {}
         if step > 0:
-            m, v = self._views(self.exp_avg), self._views(self.exp_avg_sq)
+            m, v = self.net._views(self.exp_avg), self.net._views(self.exp_avg_sq)
             state = {i: {"step": torch.tensor(float(step)), "exp_avg": m[k].clone(), "exp_avg_sq": v[k].clone()}
                      for i, k in enumerate(STATE_DICT_KEYS)}
         return {"state": state, "param_groups": [group]}
@@ -176,7 +184,7 @@ class AdamW:
         steps = set()
         m_new, v_new = torch.zeros_like(self.exp_avg), torch.zeros_like(self.exp_avg_sq)
         if state:
-            m, v = self._views(m_new), self._views(v_new)
+            m, v = self.net._views(m_new), self.net._views(v_new)
             for i, k in zip(ids, STATE_DICT_KEYS):
                 s = state[i]
                 if tuple(s["exp_avg"].shape) != tuple(m[k].shape) or tuple(s["exp_avg_sq"].shape) != tuple(m[k].shape):
@@ -244,57 +252,80 @@ def fits_fused(m: int, minibatch_size: Optional[int] = None, drop_last: bool = F
     return 1 <= fused_rows(m, minibatch_size, drop_last) <= FUSED_MAX_ROWS
 
 
-def _fused_net(net: MlpNet, opt: "AdamW") -> abi.DDPpoFusedNet:
-    hyper = abi.DDAdamWHyper(opt._lr, opt.betas[0], opt.betas[1], opt.eps, opt.weight_decay)
-    return abi.DDPpoFusedNet(opt.params.data_ptr(), opt._grad_out.data_ptr(), opt.exp_avg.data_ptr(),
-                             opt.exp_avg_sq.data_ptr(), opt._state.data_ptr(), net.packed.data_ptr(), hyper,
-                             net.ln_eps, 0)
+class _Plan(NamedTuple):
+    """One :func:`ppo_update` call, normalised by :func:`_plan`.  The full
+    batch looped keeps ``five`` as given and has None for the next three."""
+    five: tuple
+    m: Optional[int]
+    size: Optional[int]
+    ranges: Optional[list]
+    num_epochs: int
+    drop_last: bool
+    coefficients: tuple           # clip_epsilon, entropy_coef, value_coef
+    max_norm: Optional[float]
 
 
-def _ppo_update_fused(actor, critic, five, actor_opt, critic_opt, num_epochs, clip_epsilon, entropy_coef, value_coef,
-                      max_grad_norm, minibatch_size, shuffle_seed, shuffle_epoch, drop_last) -> torch.Tensor:
-    """``ppo_update``'s loop as ``dd_ppo_update_fused``: the ``[11, num_epochs,
-    steps]`` log tensor.  The argument checks of the loop it replaces, in
-    their order, then its own two limits."""
+def _plan(actor, critic, five, *, fused, num_epochs, minibatch_size, drop_last, clip_epsilon, entropy_coef,
+          value_coef, max_grad_norm) -> _Plan:
+    """What an update accepts, stated once for ``fused=True`` and the loop, in
+    the order each has always reported faults in.  ``five`` is ``(batch,)`` or
+    the five tensors.  The loop's first step checks the networks, the
+    coefficients and ``max_grad_norm`` in :func:`ppo_losses` and
+    :meth:`MlpNet.backward`, after the shuffle has checked the columns (the
+    full batch is checked there alone); ``fused=True`` calls neither, so the
+    same ``_args`` checks are made here and the scalars come back as floats."""
+    num_epochs = int(num_epochs)
+    if num_epochs < 1:
+        raise ValueError(f"num_epochs must be at least 1, got {num_epochs}")
     size = None if minibatch_size is None else int(minibatch_size)
     if size is not None and size < 1:
         raise ValueError(f"minibatch_size must be at least 1, got {minibatch_size!r}")
+    coefficients, max_norm, drop_last = (clip_epsilon, entropy_coef, value_coef), max_grad_norm, bool(drop_last)
+    if size is None and not fused:
+        return _Plan(five, None, None, None, num_epochs, drop_last, coefficients, max_norm)
     if len(five) == 1:  # a batch: its five tensors
-        if not isinstance(five[0], (PpoBatch, PpoEpisodesBatch)):
+        five = _args.batch_five(five[0])
+        if five is None:
             raise ValueError("batch must be a PpoBatch, a PpoEpisodesBatch or the five tensors")
-        five = tuple(five[0][:5])
     if len(five) != 5 or not all(isinstance(t, torch.Tensor) for t in five):
-        raise ValueError("fused=True needs all five tensors (states, actions, old_log_probs, advantages, returns)")
+        raise ValueError(f"{'fused=True needs' if fused else 'minibatches need'} all five tensors "
+                         "(states, actions, old_log_probs, advantages, returns)")
     m = int(five[0].shape[0])
-    steps = 1 if size is None else len(minibatch_ranges(m, size, drop_last))
-    if steps == 0:
-        raise ValueError(f"no minibatch to step on: {m} rows, minibatch_size {size}, drop_last={bool(drop_last)}")
-    if m == 0:
-        raise ValueError("ppo_losses needs at least one row: a mean over no rows has no value")
-    if getattr(actor, "out_dim", None) != 3 or getattr(critic, "out_dim", None) != 1:
-        raise ValueError("ppo_losses needs an MlpNet actor (out_dim 3) and an MlpNet critic (out_dim 1)")
-    if critic.device != actor.device:
-        raise ValueError(f"the actor is on {actor.device}, the critic on {critic.device}")
-    for name, c in (("clip_epsilon", clip_epsilon), ("entropy_coef", entropy_coef), ("value_coef", value_coef)):
-        if not math.isfinite(float(c)):
-            raise ValueError(f"{name} must be finite, got {c!r}")
-    if float(clip_epsilon) < 0.0:
-        raise ValueError(f"clip_epsilon must not be negative, got {clip_epsilon!r}")
-    if max_grad_norm is not None and math.isnan(float(max_grad_norm)):
-        raise ValueError("max_norm must not be NaN")
+    ranges = [(0, m)] if size is None else minibatch_ranges(m, size, drop_last)
+    if not ranges:
+        raise ValueError(f"no minibatch to step on: {m} rows, minibatch_size {size}, drop_last={drop_last}")
+    if fused:
+        _args.some_rows(m, "ppo_losses")
+        _args.check_actor_critic(actor, critic)
+        coefficients = _args.ppo_coefficients(*coefficients)
+        max_norm = _args.clip_norm(max_norm)
+    return _Plan(five, m, size, ranges, num_epochs, drop_last, coefficients, max_norm)
+
+
+def _fused_net(net: MlpNet, opt: "AdamW") -> abi.DDPpoFusedNet:
+    return abi.DDPpoFusedNet(opt.params.data_ptr(), opt.grad_buffer().data_ptr(), opt.exp_avg.data_ptr(),
+                             opt.exp_avg_sq.data_ptr(), opt._state.data_ptr(), net.packed.data_ptr(), opt._hyper(),
+                             net.ln_eps, 0)
+
+
+def _ppo_update_fused(actor, critic, plan: _Plan, actor_opt, critic_opt, shuffle_seed, shuffle_epoch) -> torch.Tensor:
+    """The steps of ``plan`` as ``dd_ppo_update_fused``: the ``[11, num_epochs,
+    steps]`` log tensor.  Its own two limits, then the columns, stacked per
+    epoch where they are shuffled, and the launch."""
     for name, net in (("actor", actor), ("critic", critic)):
         if net.compute != "f32":
             raise ValueError(f"fused=True runs compute='f32' networks only, the {name} is compute={net.compute!r}; "
                              "use fused=False")
-    rows = fused_rows(m, size, drop_last)
+    rows = max(hi - lo for lo, hi in plan.ranges)
     if rows > FUSED_MAX_ROWS:
         raise ValueError(f"fused=True takes minibatches of at most {FUSED_MAX_ROWS} rows (one row tile of the "
                          f"backward), this update has one of {rows}; pass minibatch_size <= {FUSED_MAX_ROWS} or "
                          "fused=False")
+    five, m, size, num_epochs = plan.five, plan.m, plan.size, plan.num_epochs
     dev = actor.device
     if five[0].dim() != 2 or five[0].shape[1] != abi.DD_OBS_DIM:
         raise ValueError(f"states must be [M, {abi.DD_OBS_DIM}]")
-    cols = [_column(name, t, m, dev) for name, t in zip(ShuffledBatch._fields[:5], five)]
+    cols = [_args.column(name, t, m, dev) for name, t in zip(ShuffledBatch._fields[:5], five)]
     stride = 0
     if size is not None:  # the epochs' shuffled batches, one after the other: num_epochs launches, whatever M / B is
         stacked = [torch.empty((num_epochs * m,) + tuple(c.shape[1:]), dtype=c.dtype, device=dev) for c in cols]
@@ -304,19 +335,34 @@ def _ppo_update_fused(actor, critic, five, actor_opt, critic_opt, num_epochs, cl
             shuffle_batch(cols, seed=shuffle_seed, epoch=int(shuffle_epoch) + epoch, out=out)
         cols, stride = stacked, m
     lib = actor._lib
-    ws = getattr(actor_opt, "_fused_ws", None)
-    if ws is None:  # the backward's weight images and head gradients of both networks: a fixed size, kept
-        ws = actor_opt._fused_ws = torch.empty(int(lib.dd_ppo_update_fused_workspace()) // 8, dtype=torch.int64,
-                                               device=dev)
-    logs = torch.empty(abi.DD_PPO_FUSED_LOGS, num_epochs, steps, dtype=torch.float64, device=dev)
-    fmt = abi.DD_ACT_BITMASK if cols[1].dtype == torch.uint8 else abi.DD_ACT_F32X3
+    if actor_opt._fused_ws is None:
+        actor_opt._fused_ws = torch.empty(int(lib.dd_ppo_update_fused_workspace()) // 8, dtype=torch.int64, device=dev)
+    logs = torch.empty(abi.DD_PPO_FUSED_LOGS, num_epochs, len(plan.ranges), dtype=torch.float64, device=dev)
     io = abi.DDPpoFusedIO(_fused_net(actor, actor_opt), _fused_net(critic, critic_opt), cols[0].data_ptr(),
-                          cols[1].data_ptr(), cols[2].data_ptr(), cols[3].data_ptr(), cols[4].data_ptr(), fmt,
-                          1 if drop_last else 0, m, stride, num_epochs, min(size, m) if size is not None else m,
-                          float(clip_epsilon), float(entropy_coef), float(value_coef),
-                          float(max_grad_norm) if max_grad_norm is not None else 0.0, logs.data_ptr())
-    abi.check(lib.dd_ppo_update_fused(ctypes.byref(io), ws.data_ptr(), actor._stream()), "dd_ppo_update_fused")
+                          cols[1].data_ptr(), cols[2].data_ptr(), cols[3].data_ptr(), cols[4].data_ptr(),
+                          _args.action_format(cols[1]), 1 if plan.drop_last else 0, m, stride, num_epochs,
+                          min(size, m) if size is not None else m, *plan.coefficients, plan.max_norm,
+                          logs.data_ptr())
+    abi.check(lib.dd_ppo_update_fused(ctypes.byref(io), actor_opt._fused_ws.data_ptr(), actor._stream()),
+              "dd_ppo_update_fused")
     return logs
+
+
+def _ppo_step(actor, critic, five, actor_opt, critic_opt, plan: _Plan) -> torch.Tensor:
+    """One optimizer step of each network on the rows of ``five`` (a batch or
+    five tensors); its log entries."""
+    rows = five[0] if isinstance(five[0], torch.Tensor) else five[0].states
+    clip_epsilon, entropy_coef, value_coef = plan.coefficients
+    losses = ppo_losses(actor, critic, *five, clip_epsilon=clip_epsilon, entropy_coef=entropy_coef,
+                        value_coef=value_coef, grads=True)
+    g_actor, g_critic = actor_opt.grad_buffer(), critic_opt.grad_buffer()
+    _, n_actor = actor.backward(rows, losses.grad_logits, max_norm=plan.max_norm, out=g_actor)
+    _, n_critic = critic.backward(rows, losses.grad_values, max_norm=plan.max_norm, out=g_critic)
+    actor_opt.step(g_actor)
+    critic_opt.step(g_critic)
+    s = losses.ratio_stats
+    return torch.stack([losses.total_loss, losses.policy_loss, losses.value_loss, losses.entropy,
+                        s["mean"], s["min"], s["max"], s["std"], s["clipped_frac"], n_actor, n_critic])
 
 
 def ppo_update(actor: MlpNet, critic: MlpNet, batch, actor_opt: AdamW, critic_opt: AdamW, *, num_epochs: int = 4,
@@ -364,60 +410,27 @@ def ppo_update(actor: MlpNet, critic: MlpNet, batch, actor_opt: AdamW, critic_op
     ``actor_opt.status()`` / ``critic_opt.status()``."""
     if actor_opt.net is not actor or critic_opt.net is not critic:
         raise ValueError("actor_opt must optimize actor and critic_opt critic")
-    num_epochs = int(num_epochs)
-    if num_epochs < 1:
-        raise ValueError(f"num_epochs must be at least 1, got {num_epochs}")
     five = tuple(batch) if isinstance(batch, (tuple, list)) and not hasattr(batch, "_fields") else (batch,)
-    dev = actor.device
-    scratch = getattr(actor_opt, "_grad_out", None), getattr(critic_opt, "_grad_out", None)
-    if scratch[0] is None:
-        actor_opt._grad_out = torch.empty_like(actor_opt.params)
-    if scratch[1] is None:
-        critic_opt._grad_out = torch.empty_like(critic_opt.params)
-
-    def step(five):
-        """One optimizer step of each network on the rows of ``five``; its log entries."""
-        rows = five[0] if isinstance(five[0], torch.Tensor) else five[0].states
-        losses = ppo_losses(actor, critic, *five, clip_epsilon=clip_epsilon, entropy_coef=entropy_coef,
-                            value_coef=value_coef, grads=True)
-        g_actor, n_actor = actor.backward(rows, losses.grad_logits, max_norm=max_grad_norm, out=actor_opt._grad_out)
-        g_critic, n_critic = critic.backward(rows, losses.grad_values, max_norm=max_grad_norm,
-                                             out=critic_opt._grad_out)
-        actor_opt.step(actor_opt._grad_out)
-        critic_opt.step(critic_opt._grad_out)
-        s = losses.ratio_stats
-        return torch.stack([losses.total_loss, losses.policy_loss, losses.value_loss, losses.entropy,
-                            s["mean"], s["min"], s["max"], s["std"], s["clipped_frac"], n_actor, n_critic])
-
+    plan = _plan(actor, critic, five, fused=fused, num_epochs=num_epochs, minibatch_size=minibatch_size,
+                 drop_last=drop_last, clip_epsilon=clip_epsilon, entropy_coef=entropy_coef, value_coef=value_coef,
+                 max_grad_norm=max_grad_norm)
+    num_epochs, dev = plan.num_epochs, actor.device
     if fused:
-        logs = _ppo_update_fused(actor, critic, five, actor_opt, critic_opt, num_epochs, clip_epsilon, entropy_coef,
-                                 value_coef, max_grad_norm, minibatch_size, shuffle_seed, shuffle_epoch, drop_last)
-        if minibatch_size is None:
+        logs = _ppo_update_fused(actor, critic, plan, actor_opt, critic_opt, shuffle_seed, shuffle_epoch)
+        if plan.size is None:
             logs = logs.view(len(LOG_KEYS), num_epochs)
-    elif minibatch_size is None:
+    elif plan.size is None:
         logs = torch.empty(len(LOG_KEYS), num_epochs, dtype=torch.float64, device=dev)
         for epoch in range(num_epochs):
-            logs[:, epoch] = step(five)
+            logs[:, epoch] = _ppo_step(actor, critic, plan.five, actor_opt, critic_opt, plan)
     else:
-        size = int(minibatch_size)
-        if size < 1:
-            raise ValueError(f"minibatch_size must be at least 1, got {minibatch_size!r}")
-        if len(five) == 1:  # a batch: its five tensors
-            if not isinstance(five[0], (PpoBatch, PpoEpisodesBatch)):
-                raise ValueError("batch must be a PpoBatch, a PpoEpisodesBatch or the five tensors")
-            five = tuple(five[0][:5])
-        if len(five) != 5 or not all(isinstance(t, torch.Tensor) for t in five):
-            raise ValueError("minibatches need all five tensors (states, actions, old_log_probs, advantages, returns)")
-        m = int(five[0].shape[0])
-        ranges = minibatch_ranges(m, size, drop_last)
-        if not ranges:
-            raise ValueError(f"no minibatch to step on: {m} rows, minibatch_size {size}, drop_last={bool(drop_last)}")
-        logs = torch.empty(len(LOG_KEYS), num_epochs, len(ranges), dtype=torch.float64, device=dev)
+        logs = torch.empty(len(LOG_KEYS), num_epochs, len(plan.ranges), dtype=torch.float64, device=dev)
         shuffled = None
         for epoch in range(num_epochs):
-            shuffled = shuffle_batch(five, seed=shuffle_seed, epoch=int(shuffle_epoch) + epoch, out=shuffled)
-            for i, (lo, hi) in enumerate(ranges):
-                logs[:, epoch, i] = step(tuple(t[lo:hi] for t in shuffled[:5]))
+            shuffled = shuffle_batch(plan.five, seed=shuffle_seed, epoch=int(shuffle_epoch) + epoch, out=shuffled)
+            for i, (lo, hi) in enumerate(plan.ranges):
+                logs[:, epoch, i] = _ppo_step(actor, critic, tuple(t[lo:hi] for t in shuffled[:5]), actor_opt,
+                                              critic_opt, plan)
     by_key = {k: logs[i] for i, k in enumerate(LOG_KEYS)}
     summary = {k: v.mean() for k, v in by_key.items()}
     summary["ratio_min"] = by_key["ratio_min"].min()

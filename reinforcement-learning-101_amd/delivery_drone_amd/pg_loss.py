@@ -19,20 +19,20 @@ rows are exactly 0, so it adds nothing to a parameter gradient, and the number
 of active rows is counted on the device.  Every scalar is a 0-d float64 device
 tensor summed in double over a reduction tree of fixed shape; nothing is read
 back to the host, and both update functions capture as one linear graph.
+Rows, masks and batches are checked by ``_args``, in :func:`ppo_losses`' words;
+gradients go into the optimizers' own buffers (:meth:`AdamW.grad_buffer`).
 """
 from __future__ import annotations
 
 import ctypes
-import math
 from typing import NamedTuple, Optional
 
 import torch
 
-from . import abi
+from . import _args, abi
 from .adamw import AdamW
 from .policy import MlpNet
-from .ppo_loss import _row_tensor
-from .train_batch import ReinforceBatch, ReinforceEpisodesBatch, reinforce_batch
+from .train_batch import ReinforceBatch, reinforce_batch
 
 __all__ = ["ReinforceLosses", "reinforce_losses", "ReinforceUpdate", "reinforce_update", "collect_reinforce",
            "TdLosses", "td_losses", "ActorCriticUpdate", "actor_critic_update"]
@@ -73,63 +73,25 @@ class ActorCriticUpdate(NamedTuple):
     critic_grad_norm: torch.Tensor
 
 
-def _stream(dev):
-    return ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-
-
-def _mask(active, m, dev):
-    if active is None:
-        return None
-    if (not isinstance(active, torch.Tensor) or tuple(active.shape) != (m,)
-            or active.dtype not in (torch.bool, torch.uint8)):
-        raise ValueError(f"active must be a bool or uint8 tensor of shape ({m},)")
-    if active.device != dev:
-        raise ValueError(f"active is on {active.device}, states on {dev}")
-    active = active.contiguous()
-    return active.view(torch.uint8) if active.dtype == torch.bool else active
-
-
-def _rows(states, what):
-    if not isinstance(states, torch.Tensor) or states.dim() != 2:
-        raise ValueError(f"states must be [M, {abi.DD_OBS_DIM}]")
-    m = int(states.shape[0])
-    if m == 0:
-        raise ValueError(f"{what} needs at least one row: a mean over no rows has no value")
-    return m
-
-
 def _score_losses(actor, states, actions, weights, active, grads, what):
     """evaluate_actions, then dd_pg_losses: (result, log_prob, probs, grad_logits)."""
     if not isinstance(actor, MlpNet) or actor.out_dim != 3:
         raise ValueError(f"{what} needs an MlpNet actor (out_dim 3)")
     dev = actor.device
-    m = _rows(states, what)
-    w = _row_tensor(weights, m, dev, "advantages" if what == "reinforce_losses" else "td_errors")
-    active = _mask(active, m, dev)
+    m = _args.states_rows(states, what)
+    w = _args.row_tensor(weights, m, dev, "advantages" if what == "reinforce_losses" else "td_errors")
+    active = _args.active_mask(active, m, dev)
     lp, _, probs = actor.evaluate_actions(states, actions, probs=True)
-    fmt = abi.DD_ACT_BITMASK if actions.dtype == torch.uint8 else abi.DD_ACT_F32X3
     actions = actions.contiguous()
     lib = actor._lib
     result = torch.empty(abi.DD_PG_RESULTS, dtype=torch.float64, device=dev)
     g_logits = torch.empty(m, 3, dtype=torch.float32, device=dev) if grads else None
     workspace = torch.empty(int(lib.dd_pg_loss_workspace()) // 8, dtype=torch.int64, device=dev)
-    io = abi.DDPgLossIO(lp.data_ptr(), probs.data_ptr(), actions.data_ptr(), fmt, 0, w.data_ptr(),
-                        active.data_ptr() if active is not None else None, result.data_ptr(),
+    io = abi.DDPgLossIO(lp.data_ptr(), probs.data_ptr(), actions.data_ptr(), _args.action_format(actions), 0,
+                        w.data_ptr(), active.data_ptr() if active is not None else None, result.data_ptr(),
                         g_logits.data_ptr() if grads else None)
-    abi.check(lib.dd_pg_losses(ctypes.byref(io), m, workspace.data_ptr(), _stream(dev)), "dd_pg_losses")
+    abi.check(lib.dd_pg_losses(ctypes.byref(io), m, workspace.data_ptr(), _args.stream_ptr(dev)), "dd_pg_losses")
     return result, lp, probs, g_logits
-
-
-def _unpack(states, actions, advantages, what):
-    """(states, actions, advantages, batch or None) from a batch or the three tensors."""
-    if isinstance(states, (ReinforceBatch, ReinforceEpisodesBatch)):
-        if actions is not None or advantages is not None:
-            raise ValueError("pass a batch or the three tensors, not both")
-        batch = states
-        if batch.states is None or batch.actions is None:
-            raise ValueError("the batch was built without obs or actions")
-        return batch.states, batch.actions, batch.advantages, batch
-    return states, actions, advantages, None
 
 
 def reinforce_losses(actor, states, actions=None, advantages=None, *, grads: bool = False) -> ReinforceLosses:
@@ -143,15 +105,9 @@ def reinforce_losses(actor, states, actions=None, advantages=None, *, grads: boo
     place of the three tensors.  ``grads=True`` adds the gradient of ``loss``
     at the actor's pre-Sigmoid outputs, where :meth:`MlpNet.backward` starts.
     ``M == 0`` raises.  Runs on the current stream and reads nothing back."""
-    states, actions, advantages, _ = _unpack(states, actions, advantages, "reinforce_losses")
+    states, actions, advantages, _ = _args.reinforce_columns(states, actions, advantages)
     result, lp, probs, g_logits = _score_losses(actor, states, actions, advantages, None, grads, "reinforce_losses")
     return ReinforceLosses(result[abi.DD_PG_LOSS], lp, probs, g_logits)
-
-
-def _grad_out(opt: AdamW) -> torch.Tensor:
-    if getattr(opt, "_grad_out", None) is None:
-        opt._grad_out = torch.empty_like(opt.params)
-    return opt._grad_out
 
 
 def reinforce_update(actor: MlpNet, batch, opt: AdamW, *, max_grad_norm: float = 0.5) -> ReinforceUpdate:
@@ -165,12 +121,13 @@ def reinforce_update(actor: MlpNet, batch, opt: AdamW, *, max_grad_norm: float =
     for either ``compute``; a refused ``f16x3`` step shows in ``opt.status()``."""
     if not isinstance(opt, AdamW) or opt.net is not actor:
         raise ValueError("opt must be the AdamW that optimizes actor")
-    if not isinstance(batch, (ReinforceBatch, ReinforceEpisodesBatch)):
+    states, actions, advantages, batch = _args.reinforce_columns(batch)
+    if batch is None:
         raise ValueError("reinforce_update takes a ReinforceBatch or a ReinforceEpisodesBatch")
-    out = reinforce_losses(actor, batch, grads=True)
-    _, norm = actor.backward(batch.states, out.grad_logits, max_norm=max_grad_norm, out=_grad_out(opt))
-    opt.step(opt._grad_out)
-    return ReinforceUpdate(out.loss, norm, batch.baseline, batch.std)
+    result, _, _, g_logits = _score_losses(actor, states, actions, advantages, None, True, "reinforce_losses")
+    _, norm = actor.backward(states, g_logits, max_norm=max_grad_norm, out=opt.grad_buffer())
+    opt.step(opt.grad_buffer())
+    return ReinforceUpdate(result[abi.DD_PG_LOSS], norm, batch.baseline, batch.std)
 
 
 def collect_reinforce(env, actor, max_steps: int = 300, seed: int = 0, step: int = 0, gamma: float = 0.99,
@@ -201,16 +158,14 @@ def td_losses(critic, states, rewards, next_states, dones, *, gamma: float = 0.9
     row the scalars are NaN.  Runs on the current stream and reads nothing back."""
     if not isinstance(critic, MlpNet) or critic.out_dim != 1:
         raise ValueError("td_losses needs an MlpNet critic (out_dim 1)")
-    for name, c in (("gamma", gamma), ("value_reg", value_reg)):
-        if not math.isfinite(float(c)):
-            raise ValueError(f"{name} must be finite, got {c!r}")
+    gamma, value_reg = _args.finite("gamma", gamma), _args.finite("value_reg", value_reg)
     dev = critic.device
-    m = _rows(states, "td_losses")
+    m = _args.states_rows(states, "td_losses")
     if not isinstance(next_states, torch.Tensor) or tuple(next_states.shape) != tuple(states.shape):
         raise ValueError(f"next_states must have states' shape {tuple(states.shape)}")
-    r = _row_tensor(rewards, m, dev, "rewards")
-    d = _row_tensor(dones, m, dev, "dones")
-    active = _mask(active, m, dev)
+    r = _args.row_tensor(rewards, m, dev, "rewards")
+    d = _args.row_tensor(dones, m, dev, "dones")
+    active = _args.active_mask(active, m, dev)
     values, next_values = critic(states), critic(next_states)
     lib = critic._lib
     result = torch.empty(abi.DD_TD_RESULTS, dtype=torch.float64, device=dev)
@@ -219,10 +174,10 @@ def td_losses(critic, states, rewards, next_states, dones, *, gamma: float = 0.9
     g_values = torch.empty(m, dtype=torch.float32, device=dev) if grads else None
     workspace = torch.empty(int(lib.dd_td_loss_workspace()) // 8, dtype=torch.int64, device=dev)
     io = abi.DDTdLossIO(values.data_ptr(), next_values.data_ptr(), r.data_ptr(), d.data_ptr(),
-                        active.data_ptr() if active is not None else None, float(gamma), float(value_reg),
+                        active.data_ptr() if active is not None else None, gamma, value_reg,
                         targets.data_ptr(), errors.data_ptr(), result.data_ptr(),
                         g_values.data_ptr() if grads else None)
-    abi.check(lib.dd_td_losses(ctypes.byref(io), m, workspace.data_ptr(), _stream(dev)), "dd_td_losses")
+    abi.check(lib.dd_td_losses(ctypes.byref(io), m, workspace.data_ptr(), _args.stream_ptr(dev)), "dd_td_losses")
     return TdLosses(result[abi.DD_TD_CRITIC_LOSS], result[abi.DD_TD_MSE], result[abi.DD_TD_VALUE_REG],
                     result[abi.DD_TD_COUNT], targets, errors, values, next_values, g_values)
 
@@ -255,9 +210,9 @@ def actor_critic_update(actor: MlpNet, critic: MlpNet, states, actions, rewards,
         raise ValueError(f"the actor is on {actor.device}, the critic on {critic.device}")
     td = td_losses(critic, states, rewards, next_states, dones, gamma=gamma, value_reg=value_reg, active=active,
                    grads=True)
-    _, n_critic = critic.backward(states, td.grad_values, max_norm=max_grad_norm, out=_grad_out(critic_opt))
-    critic_opt.step(critic_opt._grad_out)
+    _, n_critic = critic.backward(states, td.grad_values, max_norm=max_grad_norm, out=critic_opt.grad_buffer())
+    critic_opt.step(critic_opt.grad_buffer())
     result, _, _, g_logits = _score_losses(actor, states, actions, td.td_errors, active, True, "actor_critic_update")
-    _, n_actor = actor.backward(states, g_logits, max_norm=max_grad_norm, out=_grad_out(actor_opt))
-    actor_opt.step(actor_opt._grad_out)
+    _, n_actor = actor.backward(states, g_logits, max_norm=max_grad_norm, out=actor_opt.grad_buffer())
+    actor_opt.step(actor_opt.grad_buffer())
     return ActorCriticUpdate(result[abi.DD_PG_LOSS], td.critic_loss, td.td_errors, n_actor, n_critic)

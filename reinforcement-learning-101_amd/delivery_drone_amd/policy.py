@@ -31,7 +31,7 @@ from typing import Dict, Mapping, Optional, Tuple
 
 import torch
 
-from . import abi
+from . import _args, abi
 
 __all__ = ["MlpNet", "STATE_DICT_KEYS", "ActorPopulation", "population_summary"]
 
@@ -68,6 +68,8 @@ class MlpNet:
         self.ln_eps = float(ln_eps)
         self._src, self.out_dim = self._validated(state_dict)
         self.packed = torch.empty(int(self._lib.dd_mlp_packed_floats()), dtype=torch.float32, device=self.device)
+        self._flat = None         # flat_parameters(), once handed out
+        self._backward_ws = None  # backward()'s packed weight images and block sums: a fixed size, kept
         self._pack()
 
     def _validated(self, state_dict: Mapping[str, torch.Tensor]):
@@ -124,7 +126,7 @@ class MlpNet:
         buffer's size is the same); ``out_dim`` follows, and a launch that
         still asks for the other K gets NaN by the layout tag."""
         src, out_dim = self._validated(state_dict)
-        if getattr(self, "_flat", None) is not None:
+        if self._flat is not None:
             # flat_parameters() was handed out: the values go into that buffer, which keeps its address
             if out_dim != self.out_dim:
                 raise ValueError(f"flat_parameters() fixed the last layer at Linear(64, {self.out_dim}); "
@@ -147,16 +149,23 @@ class MlpNet:
         fixed, and the last layer's width is fixed with it.  After writing the
         buffer directly, the forward sees the new values once ``packed`` is
         rebuilt (:class:`AdamW` does that in its step)."""
-        if getattr(self, "_flat", None) is None:
+        if self._flat is None:
             flat = torch.empty(self.grad_numel(), dtype=torch.float32, device=self.device)
-            views, first = {}, 0
+            views = self._views(flat)
             for k in STATE_DICT_KEYS:
-                n = self._src[k].numel()
-                views[k] = flat[first:first + n].view(self._src[k].shape)
                 views[k].copy_(self._src[k])
-                first += n
             self._src, self._flat = views, flat
         return self._flat
+
+    def _views(self, flat: torch.Tensor) -> Dict[str, torch.Tensor]:
+        """``STATE_DICT_KEYS`` -> the parameters' shapes as views into ``flat``
+        (:meth:`grad_numel` elements), one after the other."""
+        views, first = {}, 0
+        for k in STATE_DICT_KEYS:
+            shape = self._src[k].shape
+            views[k] = flat[first:first + shape.numel()].view(shape)
+            first += shape.numel()
+        return views
 
     def state_dict(self, prefix: str = "network.") -> Dict[str, torch.Tensor]:
         """Clones of the current float32 parameters under the notebooks' keys
@@ -171,7 +180,7 @@ class MlpNet:
         return cls(torch.load(path, map_location="cpu", weights_only=True), **kw)
 
     def _stream(self):
-        return ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+        return _args.stream_ptr(self.device)
 
     def _obs(self, obs: torch.Tensor) -> torch.Tensor:
         if obs.dim() != 2 or obs.shape[1] != abi.DD_OBS_DIM:
@@ -231,11 +240,9 @@ class MlpNet:
         n = obs.shape[0]
         sampling = None
         if mode != abi.DD_SAMPLE_BERNOULLI or probs_used_out is not None:
-            if probs_used_out is not None and (
-                    tuple(probs_used_out.shape) != (n, 3) or probs_used_out.dtype != torch.float32
-                    or not probs_used_out.is_contiguous() or probs_used_out.device != self.device):
-                raise ValueError(f"probs_used_out must be a contiguous float32 tensor of shape ({n}, 3) "
-                                 f"on {self.device}")
+            if probs_used_out is not None:
+                _args.check_out(probs_used_out, (n, 3), torch.float32, self.device,
+                                "probs_used_out must be a contiguous float32 tensor")
             sampling = abi.DDSampling(mode, float(temperature),
                                       probs_used_out.data_ptr() if probs_used_out is not None else None)
         actions = actions_out if actions_out is not None else torch.empty(n, dtype=torch.uint8, device=self.device)
@@ -272,9 +279,8 @@ class MlpNet:
                              f"{tuple(actions.shape)}")
         actions = actions.contiguous()
         for name, t in (("log_prob_out", log_prob_out), ("entropy_out", entropy_out)):
-            if t is not None and (tuple(t.shape) != (n,) or t.dtype != torch.float32 or not t.is_contiguous()
-                                  or t.device != self.device):
-                raise ValueError(f"{name} must be a contiguous float32 tensor of shape ({n},) on {self.device}")
+            if t is not None:
+                _args.check_out(t, (n,), torch.float32, self.device, f"{name} must be a contiguous float32 tensor")
         lp = log_prob_out if log_prob_out is not None else torch.empty(n, dtype=torch.float32, device=self.device)
         ent = entropy_out if entropy_out is not None else torch.empty(n, dtype=torch.float32, device=self.device)
         p = torch.empty(n, 3, dtype=torch.float32, device=self.device) if probs else None
@@ -320,32 +326,23 @@ class MlpNet:
         if tuple(grad_out.shape) != want:
             raise ValueError(f"grad_out must be {want} for out_dim {self.out_dim}, got {tuple(grad_out.shape)}")
         grad_out = grad_out.detach().to(torch.float32).contiguous()
-        if max_norm is not None and math.isnan(float(max_norm)):
-            raise ValueError("max_norm must not be NaN")
+        max_norm = _args.clip_norm(max_norm)
         total = self.grad_numel()
         if out is None:
             out = torch.empty(total, dtype=torch.float32, device=self.device)
-        elif (not isinstance(out, torch.Tensor) or tuple(out.shape) != (total,) or out.dtype != torch.float32
-              or not out.is_contiguous() or out.device != self.device):
-            raise ValueError(f"out must be a contiguous float32 tensor of shape ({total},) on {self.device}")
-        shapes = dict(_SHAPES)
-        shapes["9.weight"], shapes["9.bias"] = (self.out_dim, 64), (self.out_dim,)
-        grads, first = {}, 0
-        for k in STATE_DICT_KEYS:
-            n = math.prod(shapes[k])
-            grads[k] = out[first:first + n].view(shapes[k])
-            first += n
+        else:
+            _args.check_out(out, (total,), torch.float32, self.device, "out must be a contiguous float32 tensor")
+        grads = self._views(out)
         norm = torch.empty((), dtype=torch.float64, device=self.device)
-        ws = getattr(self, "_backward_ws", None)
-        if ws is None:  # the packed weight images and the blocks' partial sums: a fixed size, kept
-            ws = self._backward_ws = torch.empty(int(self._lib.dd_mlp_backward_workspace()) // 8, dtype=torch.int64,
-                                                 device=self.device)
+        if self._backward_ws is None:
+            self._backward_ws = torch.empty(int(self._lib.dd_mlp_backward_workspace()) // 8, dtype=torch.int64,
+                                            device=self.device)
         p = abi.DDMlpParams(*[self._src[k].data_ptr() for k in STATE_DICT_KEYS], self.out_dim, self.ln_eps)
         io = abi.DDMlpBackwardIO(states.data_ptr(), grad_out.data_ptr(),
                                  abi.DDMlpGrads(*[grads[k].data_ptr() for k in STATE_DICT_KEYS]), norm.data_ptr(),
-                                 float(max_norm) if max_norm is not None else 0.0)
-        abi.check(self._lib.dd_mlp_backward(ctypes.byref(p), ctypes.byref(io), m, ws.data_ptr(), self._stream()),
-                  "dd_mlp_backward")
+                                 max_norm)
+        abi.check(self._lib.dd_mlp_backward(ctypes.byref(p), ctypes.byref(io), m, self._backward_ws.data_ptr(),
+                                            self._stream()), "dd_mlp_backward")
         return grads, norm
 
 

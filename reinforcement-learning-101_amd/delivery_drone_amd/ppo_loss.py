@@ -15,13 +15,11 @@ bits on every run and every device, and nothing is read back to the host.
 from __future__ import annotations
 
 import ctypes
-import math
 from typing import Dict, NamedTuple, Optional
 
 import torch
 
-from . import abi
-from .train_batch import PpoBatch, PpoEpisodesBatch
+from . import _args, abi
 
 __all__ = ["PpoLosses", "ppo_losses"]
 
@@ -41,15 +39,6 @@ class PpoLosses(NamedTuple):
     row_entropy: torch.Tensor              # [M] float32: each row's three factor entropies, summed
 
 
-def _row_tensor(t, m, dev, what):
-    if not isinstance(t, torch.Tensor) or tuple(t.shape) != (m,):
-        raise ValueError(f"{what} must be a tensor of shape ({m},), got "
-                         f"{tuple(t.shape) if isinstance(t, torch.Tensor) else type(t).__name__}")
-    if t.device != dev:
-        raise ValueError(f"{what} is on {t.device}, states on {dev}")
-    return t.detach().to(torch.float32).contiguous()
-
-
 def ppo_losses(actor, critic, states, actions=None, old_log_probs=None, advantages=None, returns=None,
                clip_epsilon: float = 0.2, entropy_coef: float = 0.01, value_coef: float = 0.5, *,
                grads: bool = False) -> PpoLosses:
@@ -64,34 +53,17 @@ def ppo_losses(actor, critic, states, actions=None, old_log_probs=None, advantag
     ``M == 0`` raises: a mean over no rows has no value.  Runs on the current
     stream and reads nothing back.
     """
-    if isinstance(states, (PpoBatch, PpoEpisodesBatch)):
-        if any(t is not None for t in (actions, old_log_probs, advantages, returns)):
-            raise ValueError("pass a batch or the five tensors, not both")
-        batch = states
-        if batch.states is None or batch.actions is None or batch.old_log_probs is None:
-            raise ValueError("the batch was built without obs, actions or log_prob")
-        states, actions, old_log_probs, advantages, returns = batch[:5]
-    if getattr(actor, "out_dim", None) != 3 or getattr(critic, "out_dim", None) != 1:
-        raise ValueError("ppo_losses needs an MlpNet actor (out_dim 3) and an MlpNet critic (out_dim 1)")
-    if critic.device != actor.device:
-        raise ValueError(f"the actor is on {actor.device}, the critic on {critic.device}")
-    for name, c in (("clip_epsilon", clip_epsilon), ("entropy_coef", entropy_coef), ("value_coef", value_coef)):
-        if not math.isfinite(float(c)):
-            raise ValueError(f"{name} must be finite, got {c!r}")
-    if float(clip_epsilon) < 0.0:
-        raise ValueError(f"clip_epsilon must not be negative, got {clip_epsilon!r}")
+    states, actions, old_log_probs, advantages, returns = _args.ppo_columns(states, actions, old_log_probs,
+                                                                            advantages, returns)
+    _args.check_actor_critic(actor, critic)
+    clip_epsilon, entropy_coef, value_coef = _args.ppo_coefficients(clip_epsilon, entropy_coef, value_coef)
     dev = actor.device
-    if not isinstance(states, torch.Tensor) or states.dim() != 2:
-        raise ValueError(f"states must be [M, {abi.DD_OBS_DIM}]")
-    m = int(states.shape[0])
-    if m == 0:
-        raise ValueError("ppo_losses needs at least one row: a mean over no rows has no value")
-    old = _row_tensor(old_log_probs, m, dev, "old_log_probs")
-    adv = _row_tensor(advantages, m, dev, "advantages")
-    ret = _row_tensor(returns, m, dev, "returns")
+    m = _args.states_rows(states, "ppo_losses")
+    old = _args.row_tensor(old_log_probs, m, dev, "old_log_probs")
+    adv = _args.row_tensor(advantages, m, dev, "advantages")
+    ret = _args.row_tensor(returns, m, dev, "returns")
     lp, ent, probs = actor.evaluate_actions(states, actions, probs=True)
     values = critic(states)
-    fmt = abi.DD_ACT_BITMASK if actions.dtype == torch.uint8 else abi.DD_ACT_F32X3
     actions = actions.contiguous()
     lib = actor._lib
     result = torch.empty(abi.DD_PPO_RESULTS, dtype=torch.float64, device=dev)
@@ -100,11 +72,10 @@ def ppo_losses(actor, critic, states, actions=None, old_log_probs=None, advantag
     g_values = torch.empty(m, dtype=torch.float32, device=dev) if grads else None
     workspace = torch.empty(int(lib.dd_ppo_loss_workspace()) // 8, dtype=torch.int64, device=dev)
     io = abi.DDPpoLossIO(lp.data_ptr(), ent.data_ptr(), probs.data_ptr(), values.data_ptr(), old.data_ptr(),
-                         adv.data_ptr(), ret.data_ptr(), actions.data_ptr(), fmt, 0, float(clip_epsilon),
-                         float(entropy_coef), float(value_coef), result.data_ptr(), ratio.data_ptr(),
+                         adv.data_ptr(), ret.data_ptr(), actions.data_ptr(), _args.action_format(actions), 0,
+                         clip_epsilon, entropy_coef, value_coef, result.data_ptr(), ratio.data_ptr(),
                          g_logits.data_ptr() if grads else None, g_values.data_ptr() if grads else None)
-    stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-    abi.check(lib.dd_ppo_losses(ctypes.byref(io), m, workspace.data_ptr(), stream), "dd_ppo_losses")
+    abi.check(lib.dd_ppo_losses(ctypes.byref(io), m, workspace.data_ptr(), _args.stream_ptr(dev)), "dd_ppo_losses")
     stats = {"mean": result[abi.DD_PPO_RATIO_MEAN], "min": result[abi.DD_PPO_RATIO_MIN],
              "max": result[abi.DD_PPO_RATIO_MAX], "std": result[abi.DD_PPO_RATIO_STD],
              "clipped_frac": result[abi.DD_PPO_CLIPPED_FRAC]}

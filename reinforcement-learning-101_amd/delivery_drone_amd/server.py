@@ -29,7 +29,7 @@ import socket
 import threading
 from typing import Optional
 
-from .compat import _Lanes
+from . import compat
 from .vec_env import VecDroneEnv
 
 __all__ = ["BatchSocketServer", "main"]
@@ -47,7 +47,7 @@ class BatchSocketServer:
         self.env = env
         self.num_games = env.num_envs
         self.host, self.port = host, port
-        self._lanes = _Lanes(env)
+        self._lanes = compat._Lanes(env)
         self._lock = threading.Lock()
         self._sock: Optional[socket.socket] = None
         self._threads = []

@@ -31,7 +31,7 @@ from typing import NamedTuple, Optional
 
 import torch
 
-from . import abi
+from . import _args, abi
 
 __all__ = ["PpoBatch", "ReinforceBatch", "ppo_batch", "reinforce_batch", "collect_ppo",
            "PpoEpisodesBatch", "ReinforceEpisodesBatch", "ppo_episodes_batch", "reinforce_episodes_batch",
@@ -64,10 +64,6 @@ class ReinforceBatch(NamedTuple):
     offsets: torch.Tensor
     ended: torch.Tensor
     episode_return: torch.Tensor
-
-
-def _stream(dev):
-    return ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
 
 
 def _ptr(t: Optional[torch.Tensor]):
@@ -145,8 +141,8 @@ class _PlanBase:
         stats = torch.empty(2, dtype=torch.float64, device=self.dev)
         out = torch.empty_like(x) if normalize else None
         abi.check(self.lib.dd_batch_normalize(_ptr(x) if self.M else None, _ptr(out) if self.M else None, self.M,
-                                              stats[0:].data_ptr(), stats[1:].data_ptr(),
-                                              self.workspace.data_ptr(), _stream(self.dev)), "dd_batch_normalize")
+                                              stats[0:].data_ptr(), stats[1:].data_ptr(), self.workspace.data_ptr(),
+                                              _args.stream_ptr(self.dev)), "dd_batch_normalize")
         return stats[0], stats[1], out if normalize else x
 
 
@@ -163,17 +159,17 @@ class _Plan(_PlanBase):
         self.workspace = torch.empty(int(self.lib.dd_batch_workspace(n)) // 8, dtype=torch.int64, device=dev)
         self.layout = abi.DDBatchLayout(self.lengths.data_ptr(), self.offsets.data_ptr(), self.ended.data_ptr())
         abi.check(self.lib.dd_batch_plan(self.done.data_ptr(), self.T, n, ctypes.byref(self.layout),
-                                         self.workspace.data_ptr(), _stream(dev)), "dd_batch_plan")
+                                         self.workspace.data_ptr(), _args.stream_ptr(dev)), "dd_batch_plan")
         self.M = int(self.offsets[n].item())  # the one synchronisation: the flat tensors' size
         self._episodes = n
 
     def _gather(self, io):
         abi.check(self.lib.dd_batch_gather(ctypes.byref(self.layout), ctypes.byref(io), self.T, self.n,
-                                           _stream(self.dev)), "dd_batch_gather")
+                                           _args.stream_ptr(self.dev)), "dd_batch_gather")
 
     def _advantages(self, io):
         abi.check(self.lib.dd_batch_advantages(ctypes.byref(self.layout), ctypes.byref(io), self.T, self.n,
-                                               _stream(self.dev)), "dd_batch_advantages")
+                                               _args.stream_ptr(self.dev)), "dd_batch_advantages")
 
 
 def _values(critic, rows: torch.Tensor, what: str) -> torch.Tensor:
@@ -309,7 +305,7 @@ class _EpisodePlan(_PlanBase):
         self.layout = abi.DDEpisodeLayout(self.lane_episode.data_ptr(), self.lane_row.data_ptr())
         abi.check(lib.dd_episodes_count(_ptr(self.done), _ptr(self.done_before), T, n, self.flags,
                                         ctypes.byref(self.layout), totals.data_ptr(), self.workspace.data_ptr(),
-                                        _stream(dev)), "dd_episodes_count")
+                                        _args.stream_ptr(dev)), "dd_episodes_count")
         self.E, self.M = E, M = tuple(int(v) for v in totals.tolist())  # the one synchronisation: the flat tensors' size
         self._episodes = E
         self.ep_lane = torch.empty(E, dtype=torch.int32, device=dev)
@@ -324,16 +320,16 @@ class _EpisodePlan(_PlanBase):
                                               self.ep_length.data_ptr(), self.ep_ended.data_ptr(),
                                               self.ep_offset.data_ptr())
             abi.check(lib.dd_episodes_fill(self.done.data_ptr(), _ptr(self.done_before), T, n, self.flags,
-                                           ctypes.byref(self.layout), _stream(dev)), "dd_episodes_fill")
+                                           ctypes.byref(self.layout), _args.stream_ptr(dev)), "dd_episodes_fill")
 
     def _gather(self, io):
         abi.check(self.lib.dd_episodes_gather(ctypes.byref(self.layout), self.done.data_ptr(),
                                               _ptr(self.done_before), ctypes.byref(io), self.T, self.n,
-                                              _stream(self.dev)), "dd_episodes_gather")
+                                              _args.stream_ptr(self.dev)), "dd_episodes_gather")
 
     def _advantages(self, io):
         abi.check(self.lib.dd_episodes_advantages(ctypes.byref(self.layout), ctypes.byref(io), self.T, self.n,
-                                                  _stream(self.dev)), "dd_episodes_advantages")
+                                                  _args.stream_ptr(self.dev)), "dd_episodes_advantages")
 
     def records(self):
         return (self.ep_lane, self.ep_start, self.ep_length, self.ep_offset, self.ep_ended.view(torch.bool))

@@ -78,10 +78,10 @@ def main():
         lib, lay = plan.lib, plan.layout
         ws, tot = plan.workspace, torch.empty(2, dtype=torch.int64, device=dev)
         emit(M, variant="count", **common, **timed(lambda: abi.check(lib.dd_episodes_count(
-            plan.done.data_ptr(), before.data_ptr(), T, n, 0, lay, tot.data_ptr(), ws.data_ptr(), tb._stream(dev)),
+            plan.done.data_ptr(), before.data_ptr(), T, n, 0, lay, tot.data_ptr(), ws.data_ptr(), tb._args.stream_ptr(dev)),
             "count"), w, r))
         emit(M, variant="fill", **common, **timed(lambda: abi.check(lib.dd_episodes_fill(
-            plan.done.data_ptr(), before.data_ptr(), T, n, 0, lay, tb._stream(dev)), "fill"), w, r))
+            plan.done.data_ptr(), before.data_ptr(), T, n, 0, lay, tb._args.stream_ptr(dev)), "fill"), w, r))
         for frames in (8, 16):
             emit(M, variant=f"gather_f{frames}", **common,
                  **timed(lambda: plan.gather(obs, acts, lp, tile_frames=frames), w, r))
