@@ -1262,6 +1262,77 @@ typedef struct DDPpoFusedIO {
 int64_t dd_ppo_update_fused_workspace(void);
 int dd_ppo_update_fused(const DDPpoFusedIO *io, void *workspace, void *stream);
 
+/* ---- A population of PPO learners in one fused launch (additions to ABI 13) ---
+ * dd_ppo_update_fused for every member of a population (the learners of a
+ * hyper-parameter sweep) at once.  For every member p the call leaves its
+ * parameters, both moments, both state blocks, both packed images, both gradient
+ * buffers and all DD_PPO_FUSED_LOGS log rows bit for bit as one
+ * dd_ppo_update_fused call with that member's networks, coefficients and
+ * num_epochs shuffled copies of its batch (dd_shuffle_rows with (shuffle_seed,
+ * shuffle_epoch + e), epoch_stride = m; or epoch_stride = 0 without shuffle),
+ * minibatch_size = min(minibatch_size, m) and the same drop_last leaves them.
+ *
+ * One persistent kernel of 2 * members 256-thread workgroups: block b is
+ * network b & 1 (0 actor, 1 critic) of member b >> 1.  No workgroup waits on
+ * another, so nothing needs them co-resident; past the card's CUs (one
+ * workgroup per CU) the later ones start when a CU is free.  Then one small
+ * kernel forms every member's total_loss.
+ *
+ * The batch is read in place: at minibatch i of epoch e a workgroup gathers its
+ * rows, source row perm(i size + k; m, shuffle_seed, shuffle_epoch + e) (the
+ * permutation above; i size + k when shuffle is 0), k in [0, rows), into a stage
+ * of its own in the workspace and runs the step from there.  No shuffled copy
+ * of a batch exists.  The columns need 4-byte alignment only (1 for uint8
+ * actions).
+ * num_epochs, minibatch_size and drop_last hold for every member; a member's
+ * steps follow from its own m, and its logs are [DD_PPO_FUSED_LOGS][num_epochs]
+ * [steps_p].
+ * The members' descriptors are a host array: the call turns them into a table
+ * it copies into the head of the workspace on the stream (hipMemcpyAsync from
+ * pageable memory: the array may be freed when the call returns) before the
+ * launch.  Nothing is read back.  Not for stream capture: a replay would copy
+ * from host memory that is gone.
+ * workspace: dd_ppo_update_population_workspace(members) bytes, 16-byte
+ * aligned: the table, then per workgroup the backward's weight images, the head
+ * gradient and the stage.  It grows linearly in members (0 for members < 1).
+ * hipErrorInvalidValue, before any HIP call: a null io, table or workspace, a
+ * workspace that is not 16-byte aligned; members < 1; num_epochs < 1;
+ * minibatch_size outside [1, DD_PPO_FUSED_ROWS]; for any member, what
+ * dd_ppo_update_fused refuses of a network, a column, logs, action_format, m,
+ * clip_epsilon, the two coefficients or max_grad_norm; a member with no
+ * minibatch (drop_last with m < minibatch_size); two members that share a
+ * network buffer (params, grads, a moment, state or packed overlapping). */
+typedef struct DDPpoPopulationMember {
+    DDPpoFusedNet actor;         /* K = 3                                     */
+    DDPpoFusedNet critic;        /* K = 1                                     */
+    const float *states;         /* [m][15], the batch as built: unshuffled   */
+    const void *actions;         /* uint8 [m] or float [m][3]                 */
+    const float *old_log_probs;  /* [m]                                       */
+    const float *advantages;     /* [m]                                       */
+    const float *returns;        /* [m]                                       */
+    int32_t action_format;       /* DD_ACT_BITMASK or DD_ACT_F32X3            */
+    int32_t shuffle;             /* nonzero: rows through perm                */
+    int64_t m;
+    double clip_epsilon;
+    double entropy_coef;
+    double value_coef;
+    double max_grad_norm;        /* <= 0 or inf: no clipping                  */
+    uint64_t shuffle_seed;
+    uint64_t shuffle_epoch;      /* epoch e of the call uses shuffle_epoch + e */
+    double *logs;                /* [DD_PPO_FUSED_LOGS][num_epochs][steps_p]  */
+} DDPpoPopulationMember;
+
+typedef struct DDPpoPopulationIO {
+    const DDPpoPopulationMember *table;  /* host memory, [members]            */
+    int32_t members;
+    int32_t num_epochs;
+    int32_t minibatch_size;
+    int32_t drop_last;           /* nonzero: no tail minibatch                */
+} DDPpoPopulationIO;
+
+int64_t dd_ppo_update_population_workspace(int32_t members);
+int dd_ppo_update_population(const DDPpoPopulationIO *io, void *workspace, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -2,10 +2,8 @@
 // a training batch's rows behind ppo_update's shuffled minibatch epochs
 // ("Shuffle collected data into minibatches", Actor_Critic_PPO.ipynb).
 //
-// perm(j) is stateless (include/dronestep.h has the definition): an 8-round
-// balanced Feistel network over the smallest even-width domain that holds
-// [0, m), its round function one Philox4x32-10 block keyed by (seed, epoch),
-// and cycle walking back into [0, m).  Each thread computes perm for its own
+// perm(j) is stateless (include/dronestep.h has the definition; shuffle_core.h
+// the device code and the key's set-up).  Each thread computes perm for its own
 // row once and keeps it for every column: no sort, no atomics, no workspace,
 // and the result does not depend on the launch geometry.
 //
@@ -26,40 +24,14 @@
 #include "batch_core.h"
 #include "dronestep.h"
 #include "launch.h"
-#include "philox.h"
+#include "shuffle_core.h"
 
 namespace dd {
 namespace shuffle {
 
-constexpr int kRounds = 8;  // 4 are measurably not uniform, 6 and 8 are clean (tests/test_shuffle_cpu.py)
 constexpr int kRowWords = kBlock * DD_OBS_DIM;  // one block's states
 constexpr int kPerThread = DD_OBS_DIM;          // words of the tile each thread gathers
 constexpr int kActWords = kBlock * 3;
-
-struct Key {
-    uint32_t m;       // rows
-    uint32_t h;       // bits of each Feistel half
-    uint32_t mask;    // 2^h - 1
-    uint32_t k0, k1;  // seed
-    uint32_t e0, e1;  // epoch_lo, epoch_hi ^ 0xC3C3C3C3
-};
-
-__device__ __forceinline__ uint32_t perm(uint32_t j, const Key& k) {
-    uint32_t x = j;
-    do {
-        uint32_t left = x >> k.h, right = x & k.mask;
-#pragma unroll
-        for (uint32_t r = 0; r < (uint32_t)kRounds; ++r) {
-            uint32_t o[4];
-            philox4x32_10(right, r, k.e0, k.e1, k.k0, k.k1, o);
-            const uint32_t next = left ^ (o[0] & k.mask);
-            left = right;
-            right = next;
-        }
-        x = (left << k.h) | right;
-    } while (x >= k.m);  // the cipher is a bijection of [0, 2^(2h)): the walk re-enters [0, m)
-    return x;
-}
 
 __global__ __launch_bounds__(kBlock) void indices_kernel(int32_t* __restrict__ out, Key key) {
     const uint32_t j = blockIdx.x * (uint32_t)kBlock + threadIdx.x;
@@ -152,14 +124,6 @@ __global__ __launch_bounds__(kBlock) void rows_kernel(DDShuffleIO io, Key key) {
         const int e = tail0 + (tid - head);
         dst[e] = tile[e];
     }
-}
-
-// m in [1, 2^31): the permutation's parameters
-inline Key key_of(int64_t m, uint64_t seed, uint64_t epoch) {
-    const int b = m > 1 ? 64 - __builtin_clzll((unsigned long long)(m - 1)) : 0;
-    const int h = b > 1 ? (b + 1) / 2 : 1;
-    return {(uint32_t)m, (uint32_t)h, (uint32_t)((1u << h) - 1u), (uint32_t)seed, (uint32_t)(seed >> 32),
-            (uint32_t)epoch, (uint32_t)(epoch >> 32) ^ 0xC3C3C3C3u};
 }
 
 inline bool size_ok(int64_t m) { return m >= 0 && m < (int64_t)1 << 31; }

@@ -28,7 +28,9 @@ learners: REINFORCE (:func:`collect_reinforce`, :func:`reinforce_losses`,
 :func:`reinforce_update`) and the one-step TD actor-critic
 (:func:`td_losses`, :func:`actor_critic_update`); and several actors in one
 fused launch, each on its own group of lanes (:class:`ActorPopulation`,
-:func:`population_summary`: a checkpoint tournament or a sweep's collection);
+:func:`population_summary`: a checkpoint tournament or a sweep's collection),
+and a sweep's learners updated in one fused launch (:class:`LearnerPopulation`,
+:func:`collect_ppo_population`, :func:`ppo_update_population`);
 and the frames of ``DroneGame.render`` (:meth:`VecDroneEnv.render`) and the
 labelled grid of ``--render-all`` (:meth:`VecDroneEnv.render_grid`,
 :func:`grid_shape`).
@@ -48,6 +50,7 @@ from .adamw import AdamW, PpoUpdate, ppo_update
 from .pg_loss import ReinforceLosses, ReinforceUpdate, collect_reinforce, reinforce_losses, reinforce_update
 from .pg_loss import ActorCriticUpdate, TdLosses, actor_critic_update, td_losses
 from .reward_parts import notebook_rewards
+from .population import LearnerPopulation, collect_ppo_population, ppo_update_population
 
 __all__ = [
     "EnvConfig", "VecDroneEnv", "StepInfo", "OBS_KEYS", "grid_shape",
@@ -61,5 +64,6 @@ __all__ = [
     "reinforce_losses", "ReinforceLosses", "reinforce_update", "ReinforceUpdate", "collect_reinforce",
     "td_losses", "TdLosses", "actor_critic_update", "ActorCriticUpdate",
     "notebook_rewards", "ActorPopulation", "population_summary",
+    "LearnerPopulation", "ppo_update_population", "collect_ppo_population",
 ]
 __version__ = "0.1.0"

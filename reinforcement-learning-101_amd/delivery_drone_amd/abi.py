@@ -28,7 +28,7 @@ __all__ = [
     "DD_PG_LOSS", "DD_PG_COUNT", "DD_PG_RESULTS", "DDPgLossIO",
     "DD_TD_CRITIC_LOSS", "DD_TD_MSE", "DD_TD_VALUE_REG", "DD_TD_COUNT", "DD_TD_RESULTS", "DDTdLossIO",
     "DDShuffleIO", "DD_PPO_FUSED_ROWS", "DD_PPO_POLICY_GRAD_NORM", "DD_PPO_CRITIC_GRAD_NORM", "DD_PPO_FUSED_LOGS",
-    "DDPpoFusedNet", "DDPpoFusedIO", "DD_REWARD_PARTS", "DDRewardParts", "REWARD_PART_NAMES",
+    "DDPpoFusedNet", "DDPpoFusedIO", "DDPpoPopulationMember", "DDPpoPopulationIO", "DD_REWARD_PARTS", "DDRewardParts", "REWARD_PART_NAMES",
     "sampling_mode", "lib", "load", "library_path", "check",
     "NativeLibraryError",
 ]
@@ -272,6 +272,22 @@ class DDPpoFusedIO(ctypes.Structure):
                 ("entropy_coef", _D), ("value_coef", _D), ("max_grad_norm", _D), ("logs", ctypes.c_void_p)]
 
 
+class DDPpoPopulationMember(ctypes.Structure):
+    """One learner of ``dd_ppo_update_population``: its networks, its
+    unshuffled batch, its coefficients, its shuffle key and its logs."""
+
+    _fields_ = [("actor", DDPpoFusedNet), ("critic", DDPpoFusedNet), ("states", ctypes.c_void_p),
+                ("actions", ctypes.c_void_p), ("old_log_probs", ctypes.c_void_p), ("advantages", ctypes.c_void_p),
+                ("returns", ctypes.c_void_p), ("action_format", _I), ("shuffle", _I), ("m", ctypes.c_int64),
+                ("clip_epsilon", _D), ("entropy_coef", _D), ("value_coef", _D), ("max_grad_norm", _D),
+                ("shuffle_seed", ctypes.c_uint64), ("shuffle_epoch", ctypes.c_uint64), ("logs", ctypes.c_void_p)]
+
+
+class DDPpoPopulationIO(ctypes.Structure):
+    _fields_ = [("table", ctypes.POINTER(DDPpoPopulationMember)), ("members", _I), ("num_epochs", _I),
+                ("minibatch_size", _I), ("drop_last", _I)]
+
+
 def sampling_mode(temperature) -> int:
     """The ``DD_SAMPLE_*`` mode of a notebook ``temperature``: 1 is the plain
     Bernoulli draw, 0 greedy (``probs > 0.5``), any other positive finite value
@@ -387,6 +403,8 @@ EXPORTS = {
                                        ctypes.c_void_p]),
     "dd_ppo_update_fused_workspace": (ctypes.c_int64, []),
     "dd_ppo_update_fused": (ctypes.c_int, [ctypes.POINTER(DDPpoFusedIO), ctypes.c_void_p, ctypes.c_void_p]),
+    "dd_ppo_update_population_workspace": (ctypes.c_int64, [_I]),
+    "dd_ppo_update_population": (ctypes.c_int, [ctypes.POINTER(DDPpoPopulationIO), ctypes.c_void_p, ctypes.c_void_p]),
 }
 
 #: symbols a timing-only lab build (tools/build_variants.sh) or an older
@@ -400,7 +418,8 @@ _LAB_OPTIONAL = ("dd_build_info", "dd_selftest_sqrt", "dd_rollout_kernel", "dd_s
                  "dd_adamw_state_bytes", "dd_adamw_init", "dd_adamw_step", "dd_pg_loss_workspace", "dd_pg_losses",
                  "dd_td_loss_workspace", "dd_td_losses", "dd_shuffle_indices", "dd_shuffle_rows",
                  "dd_policy_evaluate_parts", "dd_policy_rollout_population", "dd_render_grid",
-                 "dd_ppo_update_fused_workspace", "dd_ppo_update_fused")
+                 "dd_ppo_update_fused_workspace", "dd_ppo_update_fused", "dd_ppo_update_population_workspace",
+                 "dd_ppo_update_population")
 
 
 class NativeLibraryError(RuntimeError):

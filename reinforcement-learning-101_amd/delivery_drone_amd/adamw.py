@@ -308,10 +308,10 @@ def _fused_net(net: MlpNet, opt: "AdamW") -> abi.DDPpoFusedNet:
                              net.ln_eps, 0)
 
 
-def _ppo_update_fused(actor, critic, plan: _Plan, actor_opt, critic_opt, shuffle_seed, shuffle_epoch) -> torch.Tensor:
-    """The steps of ``plan`` as ``dd_ppo_update_fused``: the ``[11, num_epochs,
-    steps]`` log tensor.  Its own two limits, then the columns, stacked per
-    epoch where they are shuffled, and the launch."""
+def _fused_columns(actor, critic, plan: _Plan) -> list:
+    """What a fused update (``dd_ppo_update_fused``, ``dd_ppo_update_population``)
+    asks beyond :func:`_plan`: its own two limits, then the batch's five
+    columns as the kernels read them."""
     for name, net in (("actor", actor), ("critic", critic)):
         if net.compute != "f32":
             raise ValueError(f"fused=True runs compute='f32' networks only, the {name} is compute={net.compute!r}; "
@@ -321,11 +321,19 @@ def _ppo_update_fused(actor, critic, plan: _Plan, actor_opt, critic_opt, shuffle
         raise ValueError(f"fused=True takes minibatches of at most {FUSED_MAX_ROWS} rows (one row tile of the "
                          f"backward), this update has one of {rows}; pass minibatch_size <= {FUSED_MAX_ROWS} or "
                          "fused=False")
-    five, m, size, num_epochs = plan.five, plan.m, plan.size, plan.num_epochs
-    dev = actor.device
+    five = plan.five
     if five[0].dim() != 2 or five[0].shape[1] != abi.DD_OBS_DIM:
         raise ValueError(f"states must be [M, {abi.DD_OBS_DIM}]")
-    cols = [_args.column(name, t, m, dev) for name, t in zip(ShuffledBatch._fields[:5], five)]
+    return [_args.column(name, t, plan.m, actor.device) for name, t in zip(ShuffledBatch._fields[:5], five)]
+
+
+def _ppo_update_fused(actor, critic, plan: _Plan, actor_opt, critic_opt, shuffle_seed, shuffle_epoch) -> torch.Tensor:
+    """The steps of ``plan`` as ``dd_ppo_update_fused``: the ``[11, num_epochs,
+    steps]`` log tensor.  Its own two limits, then the columns, stacked per
+    epoch where they are shuffled, and the launch."""
+    cols = _fused_columns(actor, critic, plan)
+    m, size, num_epochs = plan.m, plan.size, plan.num_epochs
+    dev = actor.device
     stride = 0
     if size is not None:  # the epochs' shuffled batches, one after the other: num_epochs launches, whatever M / B is
         stacked = [torch.empty((num_epochs * m,) + tuple(c.shape[1:]), dtype=c.dtype, device=dev) for c in cols]
@@ -431,6 +439,11 @@ def ppo_update(actor: MlpNet, critic: MlpNet, batch, actor_opt: AdamW, critic_op
             for i, (lo, hi) in enumerate(plan.ranges):
                 logs[:, epoch, i] = _ppo_step(actor, critic, tuple(t[lo:hi] for t in shuffled[:5]), actor_opt,
                                               critic_opt, plan)
+    return _update_of(logs)
+
+
+def _update_of(logs: torch.Tensor) -> PpoUpdate:
+    """The ``[11, ...]`` log tensor of an update as its :class:`PpoUpdate`."""
     by_key = {k: logs[i] for i, k in enumerate(LOG_KEYS)}
     summary = {k: v.mean() for k, v in by_key.items()}
     summary["ratio_min"] = by_key["ratio_min"].min()
