@@ -1333,6 +1333,85 @@ typedef struct DDPpoPopulationIO {
 int64_t dd_ppo_update_population_workspace(int32_t members);
 int dd_ppo_update_population(const DDPpoPopulationIO *io, void *workspace, void *stream);
 
+/* ---- One-step actor-critic learners trained online, one launch (additions to ABI 13)
+ * Actor_Critic_Basic.ipynb's `while not all(games_done)` body for `frames`
+ * frames and every member of a population, in one launch.  Member g drives
+ * lanes [g L, (g + 1) L) of the batch `st` (L = lanes_per_member, 1 <= L <=
+ * DD_PPO_FUSED_ROWS, members L == n).  For t in [0, frames), exactly what these
+ * calls do on the member's lanes, bit for bit:
+ *   state = the lanes' rows of obs (copied)
+ *   dd_mlp_forward of the actor on state with (seed; env_id_base + lane, step + t)
+ *   dd_step with those actions (engine reward, or the notebook reward with
+ *     max_steps when shaped_hist / shaped_reward / shaped_done are set; obs,
+ *     reward, done, shaped_* are dd_step's outputs of the same names)
+ *   active = not done_prev (done_prev: the previous frame's returned done: the
+ *     shaped one when shaped, else the engine's; before frame 0, not active0,
+ *     all active when active0 is null)
+ *   dd_mlp_forward of the critic on state and on the new obs, dd_td_losses with
+ *     the returned reward and done, gamma, value_reg, the mask and grad_values,
+ *   dd_mlp_backward (max_norm = max_grad_norm) and dd_adamw_step of the critic,
+ *   dd_mlp_evaluate_actions of the actor (not yet stepped) on state, dd_pg_losses
+ *     with weights = td_errors, the mask and grad_logits,
+ *   dd_mlp_backward and dd_adamw_step of the actor.
+ * One persistent kernel of `members` 256-thread workgroups, one per member,
+ * which runs both networks one after the other; no workgroup waits on another,
+ * so past the card's CUs (one workgroup per CU) the later ones start when a CU
+ * is free.  DD_MLP_F32 networks and DD_F32 state storage only.
+ * logs: [DD_AC_LOGS][frames][members] doubles.  A frame with no active row logs
+ * NaN losses, count 0 and zero norms, and both zero-gradient steps are taken.
+ * done_last [n]: the last frame's returned done (the next call's active0 is its
+ * complement).  record_reward (float) / record_done [frames][n]: every frame's
+ * returned reward and done, both or neither.
+ * The members' descriptors are a host array, copied into the head of the
+ * workspace on the stream as dd_ppo_update_population does; not for stream
+ * capture.  Nothing is read back.
+ * workspace: dd_actor_critic_train_workspace(members) bytes, 16-byte aligned;
+ * linear in members (0 for members < 1).
+ * hipErrorInvalidValue, before any HIP call: a null cfg, st, io, table, obs,
+ * reward, done, done_last, logs or workspace; a workspace that is not 16-byte
+ * aligned; a state dd_step refuses, or not DD_F32; members < 1; frames < 1;
+ * lanes_per_member outside [1, DD_PPO_FUSED_ROWS]; members lanes_per_member !=
+ * n; shaped_mode not DD_SHAPED_PPO, or some but not all of shaped_hist,
+ * shaped_reward, shaped_done; one record buffer without the other; for any
+ * member, what dd_ppo_update_fused refuses of a network or of max_grad_norm, a
+ * gamma or value_reg that is not finite; network buffers that overlap (between
+ * members, or the actor's with the critic's). */
+enum { DD_AC_ACTOR_LOSS = 0, DD_AC_CRITIC_LOSS = 1, DD_AC_MSE = 2, DD_AC_VALUE_REG = 3, DD_AC_COUNT = 4,
+       DD_AC_ACTOR_GRAD_NORM = 5, DD_AC_CRITIC_GRAD_NORM = 6, DD_AC_LOGS = 7 };
+typedef struct DDActorCriticMember {
+    DDPpoFusedNet actor;         /* K = 3                                     */
+    DDPpoFusedNet critic;        /* K = 1                                     */
+    double gamma;                /* rounded to float32, as dd_td_losses does  */
+    double value_reg;
+    double max_grad_norm;        /* <= 0 or inf: no clipping                  */
+} DDActorCriticMember;
+
+typedef struct DDActorCriticIO {
+    const DDActorCriticMember *table;  /* host memory, [members]              */
+    int32_t members;
+    int32_t frames;
+    int64_t lanes_per_member;
+    float *obs;                  /* [n][15]: in, the current observation; out, the last frame's */
+    void *reward;                /* float [n]: the engine's, as dd_step       */
+    uint8_t *done;               /* [n]                                       */
+    double *shaped_hist;         /* [2][n] or null (all three, or none)       */
+    void *shaped_reward;         /* float [n]                                 */
+    uint8_t *shaped_done;        /* [n]                                       */
+    int32_t shaped_mode;         /* DD_SHAPED_PPO                             */
+    int32_t max_steps;           /* the notebook's timeout; <= 0: none        */
+    const uint8_t *active0;      /* nullable [n]: nonzero = trains at frame 0 */
+    uint8_t *done_last;          /* [n]                                       */
+    void *record_reward;         /* nullable float [frames][n]                */
+    uint8_t *record_done;        /* nullable [frames][n]                      */
+    uint64_t seed;
+    int64_t step;
+    double *logs;                /* [DD_AC_LOGS][frames][members]             */
+} DDActorCriticIO;
+
+int64_t dd_actor_critic_train_workspace(int32_t members);
+int dd_actor_critic_train(const DDConfig *cfg, const DDState *st, const DDActorCriticIO *io, int64_t n,
+                          void *workspace, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -38,6 +38,10 @@
 // active rows, is counted on the device with the sums.  cnt == 0: the scalars
 // are NaN (torch's mean over nothing) and every gradient row is 0.
 //
+// The row arithmetic (the parts, a row's contribution, the scalars from the
+// totals, a row's gradient) is pg_core.h's, shared with the actor-critic frame
+// loop (ac_fused.hip), which must leave these kernels' bits.
+//
 // Two launches each: the per-row work and kStatBlocks partial sums; then every
 // block adds the partials in the same tree (as ppo_dev_kernel re-totals the
 // mean) for cnt, block 0 writes result[], and all write the gradient rows.
@@ -51,28 +55,10 @@
 #include "batch_core.h"
 #include "dronestep.h"
 #include "launch.h"
+#include "pg_core.h"
 
 namespace dd {
 namespace pg {
-
-struct PgPart {
-    double s, cnt;
-    __device__ __forceinline__ PgPart& operator+=(const PgPart& b) {
-        s += b.s;
-        cnt += b.cnt;
-        return *this;
-    }
-};
-
-struct TdPart {
-    double sq, v2, cnt;
-    __device__ __forceinline__ TdPart& operator+=(const TdPart& b) {
-        sq += b.sq;
-        v2 += b.v2;
-        cnt += b.cnt;
-        return *this;
-    }
-};
 
 __device__ __forceinline__ bool is_active(const uint8_t* __restrict__ active, int64_t k) {
     return !active || active[k] != 0;
@@ -80,9 +66,7 @@ __device__ __forceinline__ bool is_active(const uint8_t* __restrict__ active, in
 
 // The unrounded TD target and error of row k.
 __device__ __forceinline__ void td_row(const DDTdLossIO& io, double gamma, int64_t k, double* target, double* delta) {
-    const double v = io.values[k], vn = io.next_values[k], r = io.rewards[k], d = io.dones[k];
-    *target = r + (gamma * vn) * (1.0 - d);
-    *delta = *target - v;
+    td_row_of(io.values[k], io.next_values[k], io.rewards[k], io.dones[k], gamma, target, delta);
 }
 
 __global__ __launch_bounds__(kBlock) void pg_rows_kernel(DDPgLossIO io, int64_t m, PgPart* __restrict__ part) {
@@ -90,8 +74,7 @@ __global__ __launch_bounds__(kBlock) void pg_rows_kernel(DDPgLossIO io, int64_t 
     PgPart acc = {0.0, 0.0};
     for (int64_t k = (int64_t)blockIdx.x * kBlock + threadIdx.x; k < m; k += (int64_t)kStatBlocks * kBlock) {
         if (!is_active(io.active, k)) continue;
-        const PgPart row = {(double)io.log_prob[k] * (double)io.weights[k], 1.0};
-        acc += row;
+        acc += pg_row(io.log_prob[k], io.weights[k]);
     }
     acc = block_sum<PgPart>(acc, sh);
     if (threadIdx.x == 0) part[blockIdx.x] = acc;
@@ -102,22 +85,17 @@ __global__ __launch_bounds__(kBlock) void pg_finish_kernel(DDPgLossIO io, int64_
     __shared__ PgPart sh[kBlock];
     const PgPart t = stat_total(part, sh);
     if (blockIdx.x == 0 && threadIdx.x == 0) {
-        io.result[DD_PG_LOSS] = -(t.s / t.cnt);
+        io.result[DD_PG_LOSS] = pg_loss_of(t);
         io.result[DD_PG_COUNT] = t.cnt;
     }
     if (!io.grad_logits) return;
     for (int64_t k = (int64_t)blockIdx.x * kBlock + threadIdx.x; k < m; k += (int64_t)kStatBlocks * kBlock) {
         float out[3] = {0.0f, 0.0f, 0.0f};
         if (is_active(io.active, k)) {
-            const double g = -((double)io.weights[k] / t.cnt);
+            const double g = pg_grad_of(io.weights[k], t.cnt);
             const uint32_t bits = given_bits(io.actions, io.action_format, k);
 #pragma unroll
-            for (int j = 0; j < 3; ++j) {
-                const float pf = io.probs[k * 3 + j];
-                double v = pf != pf ? (double)pf : 0.0;  // outside clamp_probs' range: 0 (NaN stays)
-                if (pf >= FLT_EPSILON && pf <= 1.0f - FLT_EPSILON) v = g * ((double)((bits >> j) & 1u) - (double)pf);
-                out[j] = (float)v;
-            }
+            for (int j = 0; j < 3; ++j) out[j] = pg_grad_logit_of(g, (bits >> j) & 1u, io.probs[k * 3 + j]);
         }
 #pragma unroll
         for (int j = 0; j < 3; ++j) io.grad_logits[k * 3 + j] = out[j];
@@ -132,9 +110,7 @@ __global__ __launch_bounds__(kBlock) void td_rows_kernel(DDTdLossIO io, int64_t 
         double target = 0.0, delta = 0.0;
         if (is_active(io.active, k)) {
             td_row(io, gamma, k, &target, &delta);
-            const double v = io.values[k];
-            const TdPart row = {delta * delta, v * v, 1.0};
-            acc += row;
+            acc += td_part_of(delta, io.values[k]);
         }
         io.td_targets[k] = (float)target;
         io.td_errors[k] = (float)delta;
@@ -149,7 +125,7 @@ __global__ __launch_bounds__(kBlock) void td_finish_kernel(DDTdLossIO io, int64_
     __shared__ TdPart sh[kBlock];
     const TdPart t = stat_total(part, sh);
     if (blockIdx.x == 0 && threadIdx.x == 0) {
-        const double mse = t.sq / t.cnt, reg = io.value_reg * (t.v2 / t.cnt);
+        const double mse = td_mse_of(t), reg = td_reg_of(t, io.value_reg);
         io.result[DD_TD_CRITIC_LOSS] = mse + reg;
         io.result[DD_TD_MSE] = mse;
         io.result[DD_TD_VALUE_REG] = reg;
@@ -157,13 +133,13 @@ __global__ __launch_bounds__(kBlock) void td_finish_kernel(DDTdLossIO io, int64_
     }
     if (!io.grad_values) return;
     for (int64_t k = (int64_t)blockIdx.x * kBlock + threadIdx.x; k < m; k += (int64_t)kStatBlocks * kBlock) {
-        double gv = 0.0;
+        float gv = 0.0f;
         if (is_active(io.active, k)) {
             double target, delta;
             td_row(io, gamma, k, &target, &delta);
-            gv = (-2.0 * delta + 2.0 * io.value_reg * (double)io.values[k]) / t.cnt;
+            gv = td_grad_value_of(delta, io.values[k], io.value_reg, t.cnt);
         }
-        io.grad_values[k] = (float)gv;
+        io.grad_values[k] = gv;
     }
 }
 

@@ -2,7 +2,9 @@
 // the device code of dd_ppo_update_fused (ppo_fused.hip has the design and the
 // contract) shared with dd_ppo_update_population (ppo_fused_population.hip),
 // which runs the same walk for every member of a population, so both leave the
-// same bits.
+// same bits.  The phases after a step's head gradient (backward_norm,
+// clip_adamw, repack) are functions of their own: dd_actor_critic_train
+// (ac_fused.hip) runs them inside its frame loop.
 //
 // learn<K, Rows> is parameterised on where a minibatch's rows come from:
 //   DirectRows  rows [first, first + rows) of the columns as the caller laid
@@ -136,6 +138,110 @@ __device__ __forceinline__ V stat_sum(V v, V nothing, V* sh) {
     return block_sum<V>(mine, sh);
 }
 
+// ---- one step's phases after the head gradient is written ---------------------
+// learn's, and ac_fused.hip's (the one-step actor-critic frame loop): every
+// thread of the block calls each, in this order.  LDS as learn lays it out.
+
+// A network's step count and running beta products, in registers between the
+// block's steps (the state block is written after every step).
+struct Running {
+    int64_t step;
+    double beta1_t, beta2_t;
+};
+
+__device__ __forceinline__ Running running_of(const Net& n) {
+    return {n.state->step, n.state->beta1_t, n.state->beta2_t};
+}
+
+// dd_mlp_backward of one row tile into n.grads (the weight images, then the
+// tile; n.head holds the head gradient of `rows` rows of `states`), and the
+// norm before clipping.  Starts with writes to workspace only, so the head
+// gradient needs no barrier of its own before the call.
+template <int K>
+__device__ __forceinline__ double backward_norm(const Net& n, const DDMlpParams& p, const float* states, int rows,
+                                                float* lds) {
+    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+    double* redd = reinterpret_cast<double*>(reinterpret_cast<char*>(lds) + kRedAt);
+    double* normp = reinterpret_cast<double*>(reinterpret_cast<char*>(lds) + kNormAt);
+    constexpr int kCount = adamw::params_of(K);
+    for (int idx = tid; idx < kPackedB; idx += kBlock) n.image[idx] = mlpbwd::packed_value(p, idx);
+    __syncthreads();  // the images and the head gradient are written
+    mlpbwd::backward_block<K>(p, states, n.head, rows, n.image, n.grads, 0, 1, lds);
+    __syncthreads();  // the gradient is written; LDS is free again
+
+    for (int b = wave; b < kFinishBlocks; b += kBlock / 64) {
+        double sq[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const int e = b * kBlock + 64 * j + lane;
+            sq[j] = 0.0;
+            if (e < kCount) {
+                const float f = (float)(0.0 + (double)n.grads[e]);  // the finish's sum from 0.0
+                n.grads[e] = f;
+                sq[j] = (double)f * (double)f;
+            }
+        }
+        const double s = wave_block_sum(sq);
+        if (lane == 0) normp[b] = s;
+    }
+    __syncthreads();
+    return sqrt(block_sum<double>(tid < kFinishBlocks ? normp[tid] : 0.0, redd));
+}
+
+// clip_grad_norm_ on n.grads, then the AdamW step: each thread reads and writes
+// its own elements.  Ends with the new parameters written.
+template <int K>
+__device__ __forceinline__ void clip_adamw(const Net& n, bool clip, double max_norm, double norm, Running& run) {
+    const int tid = threadIdx.x;
+    constexpr int kCount = adamw::params_of(K);
+    const double coef = clip ? mlpbwd::clip_coef(max_norm, norm) : 1.0;
+    const bool scale = !(coef == 1.0);  // a NaN factor scales, as clip_grad_norm_'s does
+    const adamw::Step now = adamw::step_of(n.opt, run.beta1_t, run.beta2_t);
+    for (int e = tid; e < kCount; e += kBlock) {
+        float g = n.grads[e];
+        if (scale) {
+            g = (float)((double)g * coef);
+            n.grads[e] = g;
+        }
+        float pn, mn, vn;
+        adamw::element(n.opt, now, n.params[e], g, n.exp_avg[e], n.exp_avg_sq[e], pn, mn, vn);
+        n.params[e] = pn;
+        n.exp_avg[e] = mn;
+        n.exp_avg_sq[e] = vn;
+    }
+    run.step += 1;
+    run.beta1_t = now.b1t;
+    run.beta2_t = now.b2t;
+    if (tid == 0) {
+        n.state->step = run.step;
+        n.state->beta1_t = run.beta1_t;
+        n.state->beta2_t = run.beta2_t;
+    }
+    __syncthreads();  // the new parameters are written
+}
+
+// dd_mlp_pack of the new parameters into n.packed.  Ends with the image
+// written and the table (the reductions' scratch) free again.
+__device__ __forceinline__ void repack(const Net& n, const DDMlpParams& p, float* lds) {
+    const int tid = threadIdx.x;
+    double* redd = reinterpret_cast<double*>(reinterpret_cast<char*>(lds) + kRedAt);
+    float* scales = reinterpret_cast<float*>(redd + kMeans);
+    for (int task = tid; task < kMeans + 3; task += kBlock) {
+        if (task < 15) redd[task] = mlp::column_mean(p.w0, 128, DD_OBS_DIM, task);
+        else if (task < 143) redd[task] = mlp::column_mean(p.w3, 128, 128, task - 15);
+        else if (task < 271) redd[task] = mlp::column_mean(p.w6, 64, 128, task - 143);
+        else if (task < kMeans) redd[task] = mlp::column_mean(task == 271 ? p.b0 : task == 272 ? p.b3 : p.b6,
+                                                              task == 273 ? 64 : 128, 1, 0);
+        else if (task == kMeans) scales[0] = mlp::act_scale_of(p.ln1_w, p.ln1_b, 128);
+        else if (task == kMeans + 1) scales[1] = mlp::act_scale_of(p.ln4_w, p.ln4_b, 128);
+        else scales[2] = mlp::act_scale_of(p.ln7_w, p.ln7_b, 64);
+    }
+    __syncthreads();
+    const PackTable table = {redd, scales};
+    for (int j = tid; j < mlp::kPacked; j += kBlock) n.packed[j] = mlp::pack_f32_at(p, j, table);
+    __syncthreads();  // the image is written; the table is free again
+}
+
 template <int K, typename Rows>
 __device__ __forceinline__ void learn(const Args& a, const Net& n, const Rows& src, float* lds) {
     constexpr bool kActor = K == 3;
@@ -143,11 +249,8 @@ __device__ __forceinline__ void learn(const Args& a, const Net& n, const Rows& s
     float* rowbuf = reinterpret_cast<float*>(reinterpret_cast<char*>(lds) + kRowsAt);
     Part* red = reinterpret_cast<Part*>(reinterpret_cast<char*>(lds) + kRedAt);
     double* redd = reinterpret_cast<double*>(red);
-    double* normp = reinterpret_cast<double*>(reinterpret_cast<char*>(lds) + kNormAt);
     const DDMlpParams p = adamw::params_view(n.params, K, n.ln_eps);
-    constexpr int kCount = adamw::params_of(K);
-    int64_t step = n.state->step;
-    double beta1_t = n.state->beta1_t, beta2_t = n.state->beta2_t;
+    Running run = running_of(n);
 
     for (int epoch = 0; epoch < a.num_epochs; ++epoch) {
         for (int i = 0; i < a.steps; ++i) {
@@ -236,74 +339,11 @@ __device__ __forceinline__ void learn(const Args& a, const Net& n, const Rows& s
                 if (tid == 0) entry[DD_PPO_VALUE_LOSS * log_row] = ppo::value_loss_of(total, md);
             }
 
-            // ---- backward: the weight images, then the one tile ------------------------
-            for (int idx = tid; idx < kPackedB; idx += kBlock) n.image[idx] = mlpbwd::packed_value(p, idx);
-            __syncthreads();  // the images and the head gradient are written
-            mlpbwd::backward_block<K>(p, states, n.head, rows, n.image, n.grads, 0, 1, lds);
-            __syncthreads();  // the gradient is written; LDS is free again
-
-            // ---- the norm before clipping ----------------------------------------------
-            for (int b = wave; b < kFinishBlocks; b += kBlock / 64) {
-                double sq[4];
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    const int e = b * kBlock + 64 * j + lane;
-                    sq[j] = 0.0;
-                    if (e < kCount) {
-                        const float f = (float)(0.0 + (double)n.grads[e]);  // the finish's sum from 0.0
-                        n.grads[e] = f;
-                        sq[j] = (double)f * (double)f;
-                    }
-                }
-                const double s = wave_block_sum(sq);
-                if (lane == 0) normp[b] = s;
-            }
-            __syncthreads();
-            const double norm = sqrt(block_sum<double>(tid < kFinishBlocks ? normp[tid] : 0.0, redd));
+            // ---- backward, the norm before clipping, clip, AdamW, re-pack ---------------
+            const double norm = backward_norm<K>(n, p, states, rows, lds);
             if (tid == 0) entry[(kActor ? DD_PPO_POLICY_GRAD_NORM : DD_PPO_CRITIC_GRAD_NORM) * log_row] = norm;
-            const double coef = a.clip ? mlpbwd::clip_coef(a.max_norm, norm) : 1.0;
-            const bool scale = !(coef == 1.0);  // a NaN factor scales, as clip_grad_norm_'s does
-
-            // ---- AdamW: each thread reads and writes its own elements ---------------------
-            const adamw::Step now = adamw::step_of(n.opt, beta1_t, beta2_t);
-            for (int e = tid; e < kCount; e += kBlock) {
-                float g = n.grads[e];
-                if (scale) {
-                    g = (float)((double)g * coef);
-                    n.grads[e] = g;
-                }
-                float pn, mn, vn;
-                adamw::element(n.opt, now, n.params[e], g, n.exp_avg[e], n.exp_avg_sq[e], pn, mn, vn);
-                n.params[e] = pn;
-                n.exp_avg[e] = mn;
-                n.exp_avg_sq[e] = vn;
-            }
-            step += 1;
-            beta1_t = now.b1t;
-            beta2_t = now.b2t;
-            if (tid == 0) {
-                n.state->step = step;
-                n.state->beta1_t = beta1_t;
-                n.state->beta2_t = beta2_t;
-            }
-            __syncthreads();  // the new parameters are written
-
-            // ---- re-pack the forward image ---------------------------------------------------
-            float* scales = reinterpret_cast<float*>(redd + kMeans);
-            for (int task = tid; task < kMeans + 3; task += kBlock) {
-                if (task < 15) redd[task] = mlp::column_mean(p.w0, 128, DD_OBS_DIM, task);
-                else if (task < 143) redd[task] = mlp::column_mean(p.w3, 128, 128, task - 15);
-                else if (task < 271) redd[task] = mlp::column_mean(p.w6, 64, 128, task - 143);
-                else if (task < kMeans) redd[task] = mlp::column_mean(task == 271 ? p.b0 : task == 272 ? p.b3 : p.b6,
-                                                                      task == 273 ? 64 : 128, 1, 0);
-                else if (task == kMeans) scales[0] = mlp::act_scale_of(p.ln1_w, p.ln1_b, 128);
-                else if (task == kMeans + 1) scales[1] = mlp::act_scale_of(p.ln4_w, p.ln4_b, 128);
-                else scales[2] = mlp::act_scale_of(p.ln7_w, p.ln7_b, 64);
-            }
-            __syncthreads();
-            const PackTable table = {redd, scales};
-            for (int j = tid; j < mlp::kPacked; j += kBlock) n.packed[j] = mlp::pack_f32_at(p, j, table);
-            __syncthreads();  // the image is written; the table is free again
+            clip_adamw<K>(n, a.clip, a.max_norm, norm, run);
+            repack(n, p, lds);
         }
     }
 }

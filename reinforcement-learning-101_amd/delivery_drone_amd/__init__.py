@@ -30,7 +30,9 @@ learners: REINFORCE (:func:`collect_reinforce`, :func:`reinforce_losses`,
 fused launch, each on its own group of lanes (:class:`ActorPopulation`,
 :func:`population_summary`: a checkpoint tournament or a sweep's collection),
 and a sweep's learners updated in one fused launch (:class:`LearnerPopulation`,
-:func:`collect_ppo_population`, :func:`ppo_update_population`);
+:func:`collect_ppo_population`, :func:`ppo_update_population`), and the
+one-step actor-critic loop itself, frame by frame, in one launch
+(:func:`actor_critic_train`, :func:`actor_critic_train_population`);
 and the frames of ``DroneGame.render`` (:meth:`VecDroneEnv.render`) and the
 labelled grid of ``--render-all`` (:meth:`VecDroneEnv.render_grid`,
 :func:`grid_shape`).
@@ -51,6 +53,7 @@ from .pg_loss import ReinforceLosses, ReinforceUpdate, collect_reinforce, reinfo
 from .pg_loss import ActorCriticUpdate, TdLosses, actor_critic_update, td_losses
 from .reward_parts import notebook_rewards
 from .population import LearnerPopulation, collect_ppo_population, ppo_update_population
+from .actor_critic import AC_LOG_KEYS, ActorCriticRun, actor_critic_train, actor_critic_train_population
 
 __all__ = [
     "EnvConfig", "VecDroneEnv", "StepInfo", "OBS_KEYS", "grid_shape",
@@ -65,5 +68,6 @@ __all__ = [
     "td_losses", "TdLosses", "actor_critic_update", "ActorCriticUpdate",
     "notebook_rewards", "ActorPopulation", "population_summary",
     "LearnerPopulation", "ppo_update_population", "collect_ppo_population",
+    "ActorCriticRun", "actor_critic_train", "actor_critic_train_population", "AC_LOG_KEYS",
 ]
 __version__ = "0.1.0"

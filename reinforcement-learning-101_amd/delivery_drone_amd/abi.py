@@ -28,7 +28,8 @@ __all__ = [
     "DD_PG_LOSS", "DD_PG_COUNT", "DD_PG_RESULTS", "DDPgLossIO",
     "DD_TD_CRITIC_LOSS", "DD_TD_MSE", "DD_TD_VALUE_REG", "DD_TD_COUNT", "DD_TD_RESULTS", "DDTdLossIO",
     "DDShuffleIO", "DD_PPO_FUSED_ROWS", "DD_PPO_POLICY_GRAD_NORM", "DD_PPO_CRITIC_GRAD_NORM", "DD_PPO_FUSED_LOGS",
-    "DDPpoFusedNet", "DDPpoFusedIO", "DDPpoPopulationMember", "DDPpoPopulationIO", "DD_REWARD_PARTS", "DDRewardParts", "REWARD_PART_NAMES",
+    "DDPpoFusedNet", "DDPpoFusedIO", "DDPpoPopulationMember", "DDPpoPopulationIO", "DDActorCriticMember",
+    "DDActorCriticIO", "DD_AC_LOGS", "AC_LOG_NAMES", "DD_REWARD_PARTS", "DDRewardParts", "REWARD_PART_NAMES",
     "sampling_mode", "lib", "load", "library_path", "check",
     "NativeLibraryError",
 ]
@@ -64,6 +65,9 @@ DD_ADAMW_REFUSED = 1
 DD_PPO_FUSED_ROWS = 128
 DD_PPO_POLICY_GRAD_NORM, DD_PPO_CRITIC_GRAD_NORM, DD_PPO_FUSED_LOGS = 9, 10, 11
 DD_PG_LOSS, DD_PG_COUNT, DD_PG_RESULTS = range(3)
+#: the log rows of ``dd_actor_critic_train``, in the header's DD_AC_* order
+AC_LOG_NAMES = ("actor_loss", "critic_loss", "mse", "value_reg", "count", "actor_grad_norm", "critic_grad_norm")
+DD_AC_LOGS = len(AC_LOG_NAMES)
 DD_TD_CRITIC_LOSS, DD_TD_MSE, DD_TD_VALUE_REG, DD_TD_COUNT, DD_TD_RESULTS = range(5)
 
 _D = ctypes.c_double
@@ -288,6 +292,23 @@ class DDPpoPopulationIO(ctypes.Structure):
                 ("minibatch_size", _I), ("drop_last", _I)]
 
 
+class DDActorCriticMember(ctypes.Structure):
+    """One learner of ``dd_actor_critic_train``: its networks and its coefficients."""
+
+    _fields_ = [("actor", DDPpoFusedNet), ("critic", DDPpoFusedNet), ("gamma", _D), ("value_reg", _D),
+                ("max_grad_norm", _D)]
+
+
+class DDActorCriticIO(ctypes.Structure):
+    _fields_ = [("table", ctypes.POINTER(DDActorCriticMember)), ("members", _I), ("frames", _I),
+                ("lanes_per_member", ctypes.c_int64), ("obs", ctypes.c_void_p), ("reward", ctypes.c_void_p),
+                ("done", ctypes.c_void_p), ("shaped_hist", ctypes.c_void_p), ("shaped_reward", ctypes.c_void_p),
+                ("shaped_done", ctypes.c_void_p), ("shaped_mode", _I), ("max_steps", _I),
+                ("active0", ctypes.c_void_p), ("done_last", ctypes.c_void_p), ("record_reward", ctypes.c_void_p),
+                ("record_done", ctypes.c_void_p), ("seed", ctypes.c_uint64), ("step", ctypes.c_int64),
+                ("logs", ctypes.c_void_p)]
+
+
 def sampling_mode(temperature) -> int:
     """The ``DD_SAMPLE_*`` mode of a notebook ``temperature``: 1 is the plain
     Bernoulli draw, 0 greedy (``probs > 0.5``), any other positive finite value
@@ -405,6 +426,10 @@ EXPORTS = {
     "dd_ppo_update_fused": (ctypes.c_int, [ctypes.POINTER(DDPpoFusedIO), ctypes.c_void_p, ctypes.c_void_p]),
     "dd_ppo_update_population_workspace": (ctypes.c_int64, [_I]),
     "dd_ppo_update_population": (ctypes.c_int, [ctypes.POINTER(DDPpoPopulationIO), ctypes.c_void_p, ctypes.c_void_p]),
+    "dd_actor_critic_train_workspace": (ctypes.c_int64, [_I]),
+    "dd_actor_critic_train": (ctypes.c_int, [ctypes.POINTER(DDConfig), ctypes.POINTER(DDState),
+                                             ctypes.POINTER(DDActorCriticIO), ctypes.c_int64, ctypes.c_void_p,
+                                             ctypes.c_void_p]),
 }
 
 #: symbols a timing-only lab build (tools/build_variants.sh) or an older
@@ -419,7 +444,7 @@ _LAB_OPTIONAL = ("dd_build_info", "dd_selftest_sqrt", "dd_rollout_kernel", "dd_s
                  "dd_td_loss_workspace", "dd_td_losses", "dd_shuffle_indices", "dd_shuffle_rows",
                  "dd_policy_evaluate_parts", "dd_policy_rollout_population", "dd_render_grid",
                  "dd_ppo_update_fused_workspace", "dd_ppo_update_fused", "dd_ppo_update_population_workspace",
-                 "dd_ppo_update_population")
+                 "dd_ppo_update_population", "dd_actor_critic_train_workspace", "dd_actor_critic_train")
 
 
 class NativeLibraryError(RuntimeError):

@@ -42,7 +42,8 @@ class LearnerPopulation(Sequence):
     ``env.policy_rollout(pop.actors, ...)`` runs the new weights.  The
     population owns the update's workspace (the descriptor table, and per
     workgroup the backward's weight images, the head gradient and the row
-    stage), allocated here once."""
+    stage), allocated here once and sized for
+    :func:`actor_critic_train_population`'s launch as well."""
 
     def __init__(self, members):
         members = tuple(tuple(m) if isinstance(m, (tuple, list)) else m for m in members)
@@ -80,7 +81,9 @@ class LearnerPopulation(Sequence):
         self._members = members
         self.device, self._lib = first.device, first._lib
         self.actors = ActorPopulation([m[0] for m in members])
-        size = int(self._lib.dd_ppo_update_population_workspace(len(members)))
+        # one workspace for either launch over the members: the PPO update's, or the actor-critic loop's
+        size = max(int(self._lib.dd_ppo_update_population_workspace(len(members))),
+                   int(self._lib.dd_actor_critic_train_workspace(len(members))))
         self._workspace = torch.empty(size // 8, dtype=torch.int64, device=self.device)
 
     def __len__(self) -> int:
