@@ -1412,6 +1412,90 @@ int64_t dd_actor_critic_train_workspace(int32_t members);
 int dd_actor_critic_train(const DDConfig *cfg, const DDState *st, const DDActorCriticIO *io, int64_t n,
                           void *workspace, void *stream);
 
+/* ---- REINFORCE learners, one iteration in one launch (additions to ABI 13) ------
+ * One iteration of Policy_Gradients.ipynb's training loop for every member of a
+ * population.  Member g drives lanes [g L, (g + 1) L) of the batch `st` (L =
+ * lanes_per_member, 1 <= L <= DD_PPO_FUSED_ROWS, members L == n), which the
+ * caller has just reset (dd_reset), on a sticky env (cfg->auto_reset == 0: one
+ * episode per lane).  Exactly what these calls do on the member's lanes, bit
+ * for bit:
+ *   dd_policy_rollout of the actor for max_steps frames with (seed; env_id_base +
+ *     lane, step + t) and the reward stream of shaped_mode / shaped_hist (the
+ *     engine's; PPO's calc_reward with shaped_hist; DD_SHAPED_REINFORCE's), the
+ *     shaped ones with the timeout env_max_steps and its -500
+ *   dd_batch_plan, dd_batch_gather, dd_batch_advantages (DD_BATCH_RETURNS, gamma
+ *     as the double it is) and dd_batch_normalize over the member's M rows (each
+ *     lane's first episode; lanes ascending, a lane's rows in frame order)
+ *   dd_mlp_evaluate_actions, dd_pg_losses with weights = the normalised returns
+ *     (the returns when normalize == 0) and grad_logits,
+ *   dd_mlp_backward (max_norm = max_grad_norm) and dd_adamw_step of the actor.
+ * One persistent kernel of `members` 256-thread workgroups, one per member; no
+ * workgroup waits on another.  The batch's rows are read in place in a
+ * frame-major record of the member's frames (no compacted copy).  The frame
+ * loop stops after the first frame that every lane of the member entered done:
+ * further frames would store the same state arrays and obs.
+ * DD_MLP_F32 networks and DD_F32 state storage only.
+ * obs [n][15]: in, the current observation; out, the last frame's.  The state
+ * arrays and shaped_hist are left as the rollout leaves them.
+ * logs: [DD_RF_LOGS][members] doubles: the loss, the gradient norm before
+ * clipping, the mean and the unbiased std of the member's returns (NaN for M <
+ * 2), and M.  lengths / ended / episode_return [n]: dd_batch_plan's and
+ * dd_batch_advantages' per lane.  record_reward (float) / record_done
+ * [max_steps][n], both or neither, and record_returns / record_advantages
+ * [max_steps][n], both or neither: each lane's rows at their frames, zeros after
+ * its episode.
+ * The members' descriptors are a host array, copied into the head of the
+ * workspace on the stream as dd_ppo_update_population does; not for stream
+ * capture.  Nothing is read back.
+ * workspace: dd_reinforce_train_workspace(members, lanes, max_steps) bytes,
+ * 16-byte aligned: linear in members, and DD_REINFORCE_CELL_BYTES per cell of a
+ * member's lanes x max_steps cells (rounded up to a multiple of 4) on top of a
+ * fixed part per member; 0 for arguments the call refuses.
+ * hipErrorInvalidValue, before any HIP call: a null cfg, st, io, table, obs,
+ * lengths, ended, episode_return, logs or workspace; a workspace that is not
+ * 16-byte aligned; a state dd_step refuses, or not DD_F32; members < 1;
+ * lanes_per_member outside [1, DD_PPO_FUSED_ROWS]; max_steps < 1, or lanes x
+ * max_steps above DD_REINFORCE_MAX_CELLS; members lanes_per_member != n;
+ * cfg->auto_reset set; an unknown shaped_mode; one buffer of a record pair
+ * without the other; for any member, what dd_ppo_update_fused refuses of a
+ * network or of max_grad_norm, a gamma that is not finite; network buffers
+ * that overlap between members. */
+#define DD_REINFORCE_CELL_BYTES 108
+#define DD_REINFORCE_MAX_CELLS (1 << 24)
+enum { DD_RF_LOSS = 0, DD_RF_GRAD_NORM = 1, DD_RF_BASELINE = 2, DD_RF_STD = 3, DD_RF_ROWS = 4, DD_RF_LOGS = 5 };
+typedef struct DDReinforceMember {
+    DDPpoFusedNet actor;         /* K = 3                                     */
+    double gamma;
+    double max_grad_norm;        /* <= 0 or inf: no clipping                  */
+} DDReinforceMember;
+
+typedef struct DDReinforceIO {
+    const DDReinforceMember *table;  /* host memory, [members]                */
+    int32_t members;
+    int32_t max_steps;           /* frames collected at most                  */
+    int64_t lanes_per_member;
+    float *obs;                  /* [n][15]                                   */
+    double *shaped_hist;         /* [2][n]: PPO's reward; null otherwise      */
+    int32_t shaped_mode;         /* DD_SHAPED_PPO or DD_SHAPED_REINFORCE      */
+    int32_t env_max_steps;       /* the shaped rewards' timeout; <= 0: none   */
+    int32_t normalize;           /* nonzero: weights = normalised returns     */
+    int32_t _pad;
+    uint64_t seed;
+    int64_t step;
+    int32_t *lengths;            /* [n]                                       */
+    uint8_t *ended;              /* [n]                                       */
+    double *episode_return;      /* [n]                                       */
+    void *record_reward;         /* nullable float [max_steps][n]             */
+    uint8_t *record_done;        /* nullable [max_steps][n]                   */
+    float *record_returns;       /* nullable [max_steps][n]                   */
+    float *record_advantages;    /* nullable [max_steps][n]                   */
+    double *logs;                /* [DD_RF_LOGS][members]                     */
+} DDReinforceIO;
+
+int64_t dd_reinforce_train_workspace(int32_t members, int64_t lanes, int32_t max_steps);
+int dd_reinforce_train(const DDConfig *cfg, const DDState *st, const DDReinforceIO *io, int64_t n, void *workspace,
+                       void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -9,6 +9,8 @@
 #include <math.h>
 #include <stdint.h>
 
+#include <type_traits>
+
 #include "batch_core.h"
 #include "dronestep.h"
 #include "launch.h"
@@ -189,11 +191,14 @@ __device__ __forceinline__ double clip_coef(double max_norm, double norm) {
 
 // One block's pass: the row tiles first_tile, first_tile + tile_step, ... of the
 // m rows, and the block's partial gradient set in the flat layout at out.  lds:
-// kLdsB bytes.
-template <int K>
+// kLdsB bytes.  Row r's observation is states[r], or with a row map (not
+// InPlace) states[where.cell(r)]: reinforce_fused.hip reads a batch's rows in
+// place in its frame-major record; grad_out is indexed by r either way.
+struct InPlace {};
+template <int K, typename Where = InPlace>
 __device__ __forceinline__ void backward_block(const DDMlpParams& p, const float* states, const float* grad_out,
                                                int64_t m, const float* packed, float* out, int64_t first_tile,
-                                               int64_t tile_step, float* lds) {
+                                               int64_t tile_step, float* lds, Where where = {}) {
     float* bufA = lds + lA;
     float* bufB = lds + lB;
     float* vec = lds + lVec;
@@ -230,8 +235,14 @@ __device__ __forceinline__ void backward_block(const DDMlpParams& p, const float
         const int64_t row = tile * kTileRows + trow;
         const bool live = row < m;
         float x[8], dz[K];
+        if constexpr (std::is_same<Where, InPlace>::value) {
 #pragma unroll
-        for (int q = 0; q < 8; ++q) x[q] = live && 2 * q + h < 15 ? states[row * 15 + 2 * q + h] : 0.0f;
+            for (int q = 0; q < 8; ++q) x[q] = live && 2 * q + h < 15 ? states[row * 15 + 2 * q + h] : 0.0f;
+        } else {
+            const int64_t cell = live ? where.cell(row) : 0;
+#pragma unroll
+            for (int q = 0; q < 8; ++q) x[q] = live && 2 * q + h < 15 ? states[cell * 15 + 2 * q + h] : 0.0f;
+        }
 #pragma unroll
         for (int k = 0; k < K; ++k) dz[k] = live ? grad_out[row * K + k] : 0.0f;
 

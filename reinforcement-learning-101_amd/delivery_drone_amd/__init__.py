@@ -32,7 +32,9 @@ fused launch, each on its own group of lanes (:class:`ActorPopulation`,
 and a sweep's learners updated in one fused launch (:class:`LearnerPopulation`,
 :func:`collect_ppo_population`, :func:`ppo_update_population`), and the
 one-step actor-critic loop itself, frame by frame, in one launch
-(:func:`actor_critic_train`, :func:`actor_critic_train_population`);
+(:func:`actor_critic_train`, :func:`actor_critic_train_population`), and
+one whole REINFORCE iteration in one launch (:class:`ReinforcePopulation`,
+:func:`reinforce_train`, :func:`reinforce_train_population`);
 and the frames of ``DroneGame.render`` (:meth:`VecDroneEnv.render`) and the
 labelled grid of ``--render-all`` (:meth:`VecDroneEnv.render_grid`,
 :func:`grid_shape`).
@@ -52,8 +54,9 @@ from .adamw import AdamW, PpoUpdate, ppo_update
 from .pg_loss import ReinforceLosses, ReinforceUpdate, collect_reinforce, reinforce_losses, reinforce_update
 from .pg_loss import ActorCriticUpdate, TdLosses, actor_critic_update, td_losses
 from .reward_parts import notebook_rewards
-from .population import LearnerPopulation, collect_ppo_population, ppo_update_population
+from .population import LearnerPopulation, ReinforcePopulation, collect_ppo_population, ppo_update_population
 from .actor_critic import AC_LOG_KEYS, ActorCriticRun, actor_critic_train, actor_critic_train_population
+from .reinforce import REINFORCE_LOG_KEYS, ReinforceRun, reinforce_train, reinforce_train_population
 
 __all__ = [
     "EnvConfig", "VecDroneEnv", "StepInfo", "OBS_KEYS", "grid_shape",
@@ -69,5 +72,6 @@ __all__ = [
     "notebook_rewards", "ActorPopulation", "population_summary",
     "LearnerPopulation", "ppo_update_population", "collect_ppo_population",
     "ActorCriticRun", "actor_critic_train", "actor_critic_train_population", "AC_LOG_KEYS",
+    "ReinforcePopulation", "ReinforceRun", "reinforce_train", "reinforce_train_population", "REINFORCE_LOG_KEYS",
 ]
 __version__ = "0.1.0"

@@ -29,7 +29,8 @@ __all__ = [
     "DD_TD_CRITIC_LOSS", "DD_TD_MSE", "DD_TD_VALUE_REG", "DD_TD_COUNT", "DD_TD_RESULTS", "DDTdLossIO",
     "DDShuffleIO", "DD_PPO_FUSED_ROWS", "DD_PPO_POLICY_GRAD_NORM", "DD_PPO_CRITIC_GRAD_NORM", "DD_PPO_FUSED_LOGS",
     "DDPpoFusedNet", "DDPpoFusedIO", "DDPpoPopulationMember", "DDPpoPopulationIO", "DDActorCriticMember",
-    "DDActorCriticIO", "DD_AC_LOGS", "AC_LOG_NAMES", "DD_REWARD_PARTS", "DDRewardParts", "REWARD_PART_NAMES",
+    "DDActorCriticIO", "DD_AC_LOGS", "AC_LOG_NAMES", "DDReinforceMember", "DDReinforceIO", "DD_RF_LOGS",
+    "RF_LOG_NAMES", "DD_REINFORCE_CELL_BYTES", "DD_REINFORCE_MAX_CELLS", "DD_REWARD_PARTS", "DDRewardParts", "REWARD_PART_NAMES",
     "sampling_mode", "lib", "load", "library_path", "check",
     "NativeLibraryError",
 ]
@@ -68,6 +69,11 @@ DD_PG_LOSS, DD_PG_COUNT, DD_PG_RESULTS = range(3)
 #: the log rows of ``dd_actor_critic_train``, in the header's DD_AC_* order
 AC_LOG_NAMES = ("actor_loss", "critic_loss", "mse", "value_reg", "count", "actor_grad_norm", "critic_grad_norm")
 DD_AC_LOGS = len(AC_LOG_NAMES)
+#: the log rows of ``dd_reinforce_train``, in the header's DD_RF_* order
+RF_LOG_NAMES = ("loss", "grad_norm", "baseline", "std", "rows")
+DD_RF_LOGS = len(RF_LOG_NAMES)
+DD_REINFORCE_CELL_BYTES = 108
+DD_REINFORCE_MAX_CELLS = 1 << 24
 DD_TD_CRITIC_LOSS, DD_TD_MSE, DD_TD_VALUE_REG, DD_TD_COUNT, DD_TD_RESULTS = range(5)
 
 _D = ctypes.c_double
@@ -309,6 +315,22 @@ class DDActorCriticIO(ctypes.Structure):
                 ("logs", ctypes.c_void_p)]
 
 
+class DDReinforceMember(ctypes.Structure):
+    """One learner of ``dd_reinforce_train``: its actor and its coefficients."""
+
+    _fields_ = [("actor", DDPpoFusedNet), ("gamma", _D), ("max_grad_norm", _D)]
+
+
+class DDReinforceIO(ctypes.Structure):
+    _fields_ = [("table", ctypes.POINTER(DDReinforceMember)), ("members", _I), ("max_steps", _I),
+                ("lanes_per_member", ctypes.c_int64), ("obs", ctypes.c_void_p), ("shaped_hist", ctypes.c_void_p),
+                ("shaped_mode", _I), ("env_max_steps", _I), ("normalize", _I), ("_pad", _I),
+                ("seed", ctypes.c_uint64), ("step", ctypes.c_int64), ("lengths", ctypes.c_void_p),
+                ("ended", ctypes.c_void_p), ("episode_return", ctypes.c_void_p), ("record_reward", ctypes.c_void_p),
+                ("record_done", ctypes.c_void_p), ("record_returns", ctypes.c_void_p),
+                ("record_advantages", ctypes.c_void_p), ("logs", ctypes.c_void_p)]
+
+
 def sampling_mode(temperature) -> int:
     """The ``DD_SAMPLE_*`` mode of a notebook ``temperature``: 1 is the plain
     Bernoulli draw, 0 greedy (``probs > 0.5``), any other positive finite value
@@ -430,6 +452,10 @@ EXPORTS = {
     "dd_actor_critic_train": (ctypes.c_int, [ctypes.POINTER(DDConfig), ctypes.POINTER(DDState),
                                              ctypes.POINTER(DDActorCriticIO), ctypes.c_int64, ctypes.c_void_p,
                                              ctypes.c_void_p]),
+    "dd_reinforce_train_workspace": (ctypes.c_int64, [_I, ctypes.c_int64, _I]),
+    "dd_reinforce_train": (ctypes.c_int, [ctypes.POINTER(DDConfig), ctypes.POINTER(DDState),
+                                          ctypes.POINTER(DDReinforceIO), ctypes.c_int64, ctypes.c_void_p,
+                                          ctypes.c_void_p]),
 }
 
 #: symbols a timing-only lab build (tools/build_variants.sh) or an older
@@ -444,7 +470,8 @@ _LAB_OPTIONAL = ("dd_build_info", "dd_selftest_sqrt", "dd_rollout_kernel", "dd_s
                  "dd_td_loss_workspace", "dd_td_losses", "dd_shuffle_indices", "dd_shuffle_rows",
                  "dd_policy_evaluate_parts", "dd_policy_rollout_population", "dd_render_grid",
                  "dd_ppo_update_fused_workspace", "dd_ppo_update_fused", "dd_ppo_update_population_workspace",
-                 "dd_ppo_update_population", "dd_actor_critic_train_workspace", "dd_actor_critic_train")
+                 "dd_ppo_update_population", "dd_actor_critic_train_workspace", "dd_actor_critic_train",
+                 "dd_reinforce_train_workspace", "dd_reinforce_train")
 
 
 class NativeLibraryError(RuntimeError):

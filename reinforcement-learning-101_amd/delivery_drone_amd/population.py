@@ -27,7 +27,7 @@ from .adamw import AdamW, FUSED_MAX_ROWS, PpoUpdate
 from .policy import ActorPopulation, MlpNet
 from .train_batch import PpoBatch, ppo_batch
 
-__all__ = ["LearnerPopulation", "ppo_update_population", "collect_ppo_population"]
+__all__ = ["LearnerPopulation", "ReinforcePopulation", "ppo_update_population", "collect_ppo_population"]
 
 
 class LearnerPopulation(Sequence):
@@ -71,15 +71,8 @@ class LearnerPopulation(Sequence):
                 if id(net) in seen:
                     raise ValueError(f"member {p}: its {name} is in the population already")
                 seen.add(id(net))
-        first = members[0][0]
-        for p, (actor, critic, _, _) in enumerate(members):
-            for net in (actor, critic):
-                if net.device != first.device:
-                    raise ValueError(f"member {p}: on {net.device}, member 0 on {first.device}")
-                if net._lib is not first._lib:
-                    raise ValueError(f"member {p}: uses another build of the library than member 0")
         self._members = members
-        self.device, self._lib = first.device, first._lib
+        self.device, self._lib = _one_device_and_library([(m[0], m[1]) for m in members])
         self.actors = ActorPopulation([m[0] for m in members])
         # one workspace for either launch over the members: the PPO update's, or the actor-critic loop's
         size = max(int(self._lib.dd_ppo_update_population_workspace(len(members))),
@@ -91,6 +84,73 @@ class LearnerPopulation(Sequence):
 
     def __getitem__(self, p):
         return self._members[p]
+
+
+def _one_device_and_library(nets_of_members):
+    """The device and the library all the members' networks share, or a
+    ``ValueError`` naming the first member that differs from member 0."""
+    first = nets_of_members[0][0]
+    for p, nets in enumerate(nets_of_members):
+        for net in nets:
+            if net.device != first.device:
+                raise ValueError(f"member {p}: on {net.device}, member 0 on {first.device}")
+            if net._lib is not first._lib:
+                raise ValueError(f"member {p}: uses another build of the library than member 0")
+    return first.device, first._lib
+
+
+class ReinforcePopulation(Sequence):
+    """The learners of a REINFORCE sweep, which have no critic: ``members`` is
+    a non-empty sequence of ``(actor, opt)``, each what
+    :func:`reinforce_update` takes (``opt`` optimizes ``actor``), all
+    ``compute="f32"``, on one device and of one library; no actor may appear
+    twice.  Anything else raises ``ValueError`` naming the member.  The
+    critic-less twin of :class:`LearnerPopulation`.
+
+    ``actors`` is the :class:`ActorPopulation` of the members' actors, built
+    once: an update rewrites each packed image in place, so the next
+    ``env.policy_rollout(pop.actors, ...)`` runs the new weights.  The
+    population owns :func:`reinforce_train_population`'s workspace, which
+    depends on the lanes per member and the frames of a call: it is allocated
+    at the first call and grown when a later call needs more."""
+
+    def __init__(self, members):
+        members = tuple(tuple(m) if isinstance(m, (tuple, list)) else m for m in members)
+        if not members:
+            raise ValueError("ReinforcePopulation needs at least one member")
+        seen = set()
+        for p, member in enumerate(members):
+            if not isinstance(member, tuple) or len(member) != 2:
+                raise ValueError(f"member {p}: expected (actor, opt)")
+            actor, opt = member
+            if not isinstance(actor, MlpNet) or actor.out_dim != 3:
+                raise ValueError(f"member {p}: the actor must be an MlpNet with out_dim 3")
+            if not isinstance(opt, AdamW):
+                raise ValueError(f"member {p}: opt must be an AdamW optimizer")
+            if opt.net is not actor:
+                raise ValueError(f"member {p}: opt must be the AdamW that optimizes actor")
+            if actor.compute != "f32":
+                raise ValueError(f"member {p}: a population update runs compute='f32' networks only, the actor "
+                                 f"is compute={actor.compute!r}")
+            if id(actor) in seen:
+                raise ValueError(f"member {p}: its actor is in the population already")
+            seen.add(id(actor))
+        self._members = members
+        self.device, self._lib = _one_device_and_library([(m[0],) for m in members])
+        self.actors = ActorPopulation([m[0] for m in members])
+        self._workspace = None
+
+    def __len__(self) -> int:
+        return len(self._members)
+
+    def __getitem__(self, p):
+        return self._members[p]
+
+    def _workspace_for(self, lanes: int, max_steps: int) -> torch.Tensor:
+        size = int(self._lib.dd_reinforce_train_workspace(len(self), lanes, max_steps))
+        if self._workspace is None or self._workspace.numel() * 8 < size:
+            self._workspace = torch.empty((size + 7) // 8, dtype=torch.int64, device=self.device)
+        return self._workspace
 
 
 def _per_member(name: str, value, members: int) -> list:
