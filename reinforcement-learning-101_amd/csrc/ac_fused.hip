@@ -16,8 +16,10 @@
 //      gives, which is actor_sample's own) and the probabilities stay in LDS;
 //   2. the frame, thread k the member's lane k: the lane's state from the env's
 //      arrays, frame.h's frame as step_tile.h's finish_lane runs it (re-spawn, sticky
-//      done, the notebook reward with its history and timeout), the state, the
-//      outputs and the new observation row stored as dd_step leaves them;
+//      done, the notebook reward with its history and timeout: frame.h's
+//      shaped_tail for the PPO shape, written out in the kernel, see there), the
+//      state (lane_io.h load_lane / store_lane), the outputs and the new
+//      observation row stored as dd_step leaves them;
 //   3. the critic's image into LDS, its forward on state and on the new rows;
 //   4. the TD rows and totals (pg_core.h), the head gradient;
 //   5. the critic's backward, norm, clip, AdamW and re-pack (ppo_fused_core.h);
@@ -40,7 +42,6 @@
 // stored with ordinary vector stores.  The env state lives in the env's arrays
 // between frames; no lane holds it in registers across a backward.  The member
 // table is uploaded into the head of the workspace and only ever read.
-#include <algorithm>
 #include <vector>
 
 #include "frame.h"
@@ -51,12 +52,12 @@
 namespace dd {
 namespace acf {
 
-using fused::kLds;
 using fused::kNetWorkspace;
 using fused::kRedAt;
 using fused::kRowFloats;
 using fused::kRowsAt;
 using fused::kTileRows;
+using fused::load_image;
 using fused::Net;
 using mlp::f32x4;
 
@@ -113,14 +114,9 @@ __device__ __forceinline__ double update(const Net& n, const Member& mb, const f
     return norm;
 }
 
-// A network's packed image into LDS (all threads; a barrier follows at the caller).
-__device__ __forceinline__ void load_image(const float* packed, float* lds) {
-    f32x4* lds4 = reinterpret_cast<f32x4*>(lds);
-    const f32x4* src4 = reinterpret_cast<const f32x4*>(packed);
-    for (int j = threadIdx.x; j < mlp::kPacked / 4; j += kBlock) lds4[j] = src4[j];
-}
-
 // Layer 1's B operand of row d of `rows_at` [rows][15] for this lane half (zero past column 14 and row `rows`).
+// The kernel keeps this index form: with ppo_fused_core.h's row-pointer load_row it spilled one to two more
+// SGPRs than before (profiles/fused_share/), and its instructions stay as they were this way.
 __device__ __forceinline__ void load_row(const float* rows_at, int d, bool live, int h, float (&x)[8]) {
 #pragma unroll
     for (int q = 0; q < 8; ++q) {
@@ -192,9 +188,7 @@ __global__ __launch_bounds__(kBlock) void train_kernel(const Member* __restrict_
             const uint32_t act = __float_as_uint(rowbuf[tid * kRowFloats + rBits]);
             const int64_t env = soa.env_id_base + d;
             Lane s;
-            s.x = soa.x[d]; s.y = soa.y[d]; s.vx = soa.vx[d]; s.vy = soa.vy[d]; s.angle = soa.angle[d];
-            s.omega = soa.omega[d]; s.fuel = soa.fuel[d]; s.px = soa.px[d]; s.py = soa.py[d]; s.total = soa.total[d];
-            s.status = soa.status[d]; s.steps = soa.steps[d]; s.episode = soa.episode[d];
+            load_lane(soa, d, s);
             double h0 = 0.0, h1 = 0.0;  // the notebook reward's two-frame distance history
             if (shaped) { h0 = a.shaped_hist[d]; h1 = a.shaped_hist[a.n + d]; }
             const bool was_done = (s.status & DD_ST_DONE) != 0;
@@ -206,7 +200,12 @@ __global__ __launch_bounds__(kBlock) void train_kernel(const Member* __restrict_
             } else {
                 reward = frame_checked<kRef, false>(k, sw, act, s);  // dd_step's frame, with its exact redo
             }
-            if (shaped) {  // dd_step's notebook path
+            // dd_step's notebook path.  The tail below is frame.h's shaped_tail (ppo, this kernel's re-spawn
+            // case) written out, and the history's pair is loaded and stored by hand: with shaped_tail the kernel
+            // spilled two more SGPRs than before, with load_hist / store_hist its instructions changed
+            // (profiles/fused_share/).  A fix to shaped_tail belongs here too; tests/test_gpu_shaped_tail.py
+            // holds the two to the same bits.
+            if (shaped) {
                 double v[13];
                 observe_values<false, true>(k, s, v);  // the notebook reward's doubles: exact quotients
                 double sr = 0.0;
@@ -246,10 +245,7 @@ __global__ __launch_bounds__(kBlock) void train_kernel(const Member* __restrict_
                 a.record_done[(int64_t)f * a.n + d] = (uint8_t)(done_f ? 1 : 0);
             }
             observe(k, s, tile + tid * DD_OBS_DIM);  // from the unrounded frame, like dd_step's obs
-            soa.x[d] = (float)s.x; soa.y[d] = (float)s.y; soa.vx[d] = (float)s.vx; soa.vy[d] = (float)s.vy;
-            soa.angle[d] = (float)s.angle; soa.omega[d] = (float)s.omega; soa.fuel[d] = (float)s.fuel;
-            soa.px[d] = (float)s.px; soa.py[d] = (float)s.py; soa.total[d] = (float)s.total;
-            soa.status[d] = (uint8_t)s.status; soa.steps[d] = s.steps; soa.episode[d] = s.episode;
+            store_lane(soa, d, s);
         }
         __syncthreads();  // the new rows are in the tile
 
@@ -327,30 +323,6 @@ __global__ __launch_bounds__(kBlock) void train_kernel(const Member* __restrict_
     if (mine) a.done_last[d] = (uint8_t)(done_prev ? 1 : 0);
 }
 
-// A network buffer of a member, for the check that no two networks share one.
-struct Owned {
-    uintptr_t first, last;  // [first, last)
-};
-
-inline void owned_of(const DDPpoFusedNet& n, int k, std::vector<Owned>& out) {
-    const uintptr_t floats = (uintptr_t)adamw::params_of(k) * sizeof(float);
-    const float* flat[4] = {n.params, n.grads, n.exp_avg, n.exp_avg_sq};
-    for (const float* p : flat) out.push_back({(uintptr_t)p, (uintptr_t)p + floats});
-    out.push_back({(uintptr_t)n.state, (uintptr_t)n.state + sizeof(DDAdamWState)});
-    out.push_back({(uintptr_t)n.packed, (uintptr_t)n.packed + (uintptr_t)mlp::kPacked * sizeof(float)});
-}
-
-// Whether any two of the buffers overlap.
-inline bool any_overlap(std::vector<Owned>& v) {
-    std::sort(v.begin(), v.end(), [](const Owned& x, const Owned& y) { return x.first < y.first; });
-    uintptr_t end = 0;
-    for (const Owned& r : v) {
-        if (r.first < end) return true;
-        end = std::max(end, r.last);
-    }
-    return false;
-}
-
 }  // namespace acf
 }  // namespace dd
 
@@ -378,8 +350,9 @@ int dd_actor_critic_train(const DDConfig* cfg, const DDState* st, const DDActorC
     const int32_t members = io->members;
     char* blocks = static_cast<char*>(workspace) + table_bytes(members);
     std::vector<Member> table((size_t)members);
-    std::vector<Owned> owned;
+    std::vector<dd::fused::Owned> owned;  // every buffer its own owner: no two may overlap
     owned.reserve((size_t)members * 12);
+    int32_t owner = 0;
     for (int32_t p = 0; p < members; ++p) {
         const DDActorCriticMember& m = io->table[p];
         if (!dd::fused::net_ok(m.actor) || !dd::fused::net_ok(m.critic)) return hipErrorInvalidValue;
@@ -392,12 +365,12 @@ int dd_actor_critic_train(const DDConfig* cfg, const DDState* st, const DDActorC
         t.gamma = (double)(float)m.gamma;
         t.value_reg = m.value_reg;
         t.max_norm = m.max_grad_norm;
-        t.clip = m.max_grad_norm > 0.0 && __builtin_isfinite(m.max_grad_norm) ? 1 : 0;
+        t.clip = dd::fused::clip_of(m.max_grad_norm) ? 1 : 0;
         t._pad = 0;
-        owned_of(m.actor, 3, owned);
-        owned_of(m.critic, 1, owned);
+        dd::fused::owned_apart(m.actor, 3, owner, owned);
+        dd::fused::owned_apart(m.critic, 1, owner, owned);
     }
-    if (any_overlap(owned)) return hipErrorInvalidValue;
+    if (dd::fused::shared_between_owners(owned)) return hipErrorInvalidValue;
 
     Args a{};
     a.k = dd::make_consts(*cfg);
@@ -423,19 +396,10 @@ int dd_actor_critic_train(const DDConfig* cfg, const DDState* st, const DDActorC
     const bool ref = dd::uses_reference_physics(*cfg);
 
     hipStream_t s = static_cast<hipStream_t>(stream);
-    // from pageable memory the copy has left `table` when the call returns
-    hipError_t e = hipMemcpyAsync(workspace, table.data(), (size_t)table_bytes(members), hipMemcpyHostToDevice, s);
-    if (e != hipSuccess) return (int)e;
-    const Member* device_table = static_cast<const Member*>(workspace);
     return dd::with_bool(ref, [&](auto r) {
-        constexpr bool kRef = decltype(r)::value;
-        // the LDS exceeds the 64 KB default; the attribute is per device, so it is set on every launch
-        const hipError_t err = hipFuncSetAttribute((const void*)train_kernel<kRef>,
-                                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLds);
-        if (err != hipSuccess) return (int)err;
-        hipLaunchKernelGGL(train_kernel<kRef>, dim3((unsigned)members), dim3(dd::kBlock), kLds, s, device_table, blocks,
-                           a, soa);
-        return dd::finish();
+        const hipError_t e = dd::fused::launch_with_table(train_kernel<decltype(r)::value>, table, workspace,
+                                                          (unsigned)members, s, blocks, a, soa);
+        return e != hipSuccess ? (int)e : dd::finish();
     });
 }
 

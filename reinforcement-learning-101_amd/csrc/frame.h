@@ -1,8 +1,11 @@
 // frame.h — one drone's frame of DroneGame.step in IEEE double: world
 // constants, the lane state, Drone.apply_thrust / update, the reward cascade,
-// get_state's observation row and the notebooks' calc_reward.  Shared by the
-// step / rollout kernels (step.hip, rollout.hip) and the fused policy loops
-// (policy_rollout.hip, policy_eval.hip), so every path evaluates the same frame bit for bit.
+// get_state's observation row, the notebooks' calc_reward and the shaped tail
+// of a frame (shaped_tail).  Shared by the step / rollout kernels (step.hip,
+// rollout.hip), the fused policy loops (policy_rollout.hip, policy_eval.hip)
+// and the fused trainers (ac_fused.hip, reinforce_fused.hip; shaped_tail:
+// policy_rollout.hip and reinforce_fused.hip), so every path
+// evaluates the same frame bit for bit.
 // The SoA plumbing around it (typed state pointers, lane loads and stores) is
 // lane_io.h's.  Compiled with -ffp-contract=off (see rollout.hip).
 #pragma once
@@ -775,6 +778,47 @@ __device__ __forceinline__ double reinforce_reward(const double v[13], uint32_t 
     const double crash_term = dist > 0.3 ? -200.0 - 100.0 : -200.0;
     total += landed ? 500.0 + fuel * 100.0 : crashed ? crash_term : 0.0;
     return total;
+}
+
+// The notebook-reward tail of one frame of a loop that carries PPO's two-frame
+// distance history in registers (policy_rollout.hip, reinforce_fused.hip;
+// ac_fused.hip's kernel keeps a written-out copy of the PPO case, which a
+// change here must follow): `v` is the frame's double observation of `s`, h0 / h1
+// the history's even and odd slot (a frame with an odd step count reads and
+// rewrites h1, an even one h0; REINFORCE's reward has no history).  A lane that
+// was done before the frame is either re-spawned (prev_state None: the history
+// restarts, not done) or sticky (done, the history untouched), reward 0 either
+// way.  max_steps > 0 is the collection loops' timeout: -500 unless landed,
+// done, and DD_ST_DONE set in s.status.  A caller for which a case cannot
+// occur passes a constant (ppo = true, respawned = false).  sr is the shaped
+// reward, the return value the shaped done.
+__device__ __forceinline__ bool shaped_tail(const double v[13], Lane& s, bool ppo, bool was_done, bool respawned,
+                                            int32_t max_steps, double& h0, double& h1, double& sr) {
+    sr = 0.0;
+    bool sd;
+    if (respawned) {
+        h0 = v[9];
+        h1 = __builtin_nan("");
+        sd = false;
+    } else if (was_done) {
+        sd = true;
+    } else {
+        if (ppo) {
+            const bool odd = (s.steps & 1) != 0;
+            sr = notebook_reward(v, s.status, odd ? h1 : h0);
+            h1 = odd ? v[9] : h1;
+            h0 = odd ? h0 : v[9];
+        } else {
+            sr = reinforce_reward(v, s.status);
+        }
+        sd = (s.status & DD_ST_DONE) != 0;
+        if (max_steps > 0 && s.steps >= max_steps) {
+            sr = (s.status & DD_ST_LANDED) ? sr : sr - 500;
+            sd = true;
+            s.status |= DD_ST_DONE;
+        }
+    }
+    return sd;
 }
 
 // The component forms: calc_reward's whole dict instead of its 'total', for the

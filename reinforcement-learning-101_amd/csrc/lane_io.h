@@ -1,7 +1,10 @@
 // lane_io.h — device-side SoA access shared by the step, rollout and
-// environment kernels (step.hip, rollout.hip, env_ops.hip) and the fused
-// policy rollout (policy_rollout.hip): block and chunk sizes, the typed view
-// of a DDState, lane loads and stores, the observation tile flushes.
+// environment kernels (step.hip, rollout.hip, env_ops.hip), the fused policy
+// loops (policy_rollout.hip, policy_eval.hip) and the fused trainers
+// (ac_fused.hip, reinforce_fused.hip): block and chunk sizes, the typed view
+// of a DDState, lane loads and stores (by 32-bit offset for the step and
+// rollout kernels, load_lane / store_lane and the reward history's pair for
+// the loops that hold a lane in registers), the observation tile flushes.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -119,6 +122,39 @@ __device__ __forceinline__ void store_spawn(const Soa<T>& a, uint32_t i, const L
     at(a.status, i) = (uint8_t)s.status;
     at(a.steps, i) = s.steps;
     at(a.episode, i) = s.episode;
+}
+
+// A whole lane between the SoA and a Lane by its 64-bit index, for the loops
+// that hold a lane in registers across frames (policy_rollout.hip,
+// policy_eval.hip, ac_fused.hip, reinforce_fused.hip); the step and rollout
+// kernels keep the 32-bit offset forms above.  kEpisode = false is for a loop
+// that never re-spawns: the episode counter is neither read (0) nor written.
+template <bool kEpisode = true, typename T>
+__device__ __forceinline__ void load_lane(const Soa<T>& a, int64_t d, Lane& s) {
+    s.x = a.x[d]; s.y = a.y[d]; s.vx = a.vx[d]; s.vy = a.vy[d]; s.angle = a.angle[d]; s.omega = a.omega[d];
+    s.fuel = a.fuel[d]; s.px = a.px[d]; s.py = a.py[d]; s.total = a.total[d];
+    s.status = a.status[d]; s.steps = a.steps[d];
+    s.episode = kEpisode ? a.episode[d] : 0;
+}
+
+template <bool kEpisode = true, typename T>
+__device__ __forceinline__ void store_lane(const Soa<T>& a, int64_t d, const Lane& s) {
+    a.x[d] = (T)s.x; a.y[d] = (T)s.y; a.vx[d] = (T)s.vx; a.vy[d] = (T)s.vy; a.angle[d] = (T)s.angle;
+    a.omega[d] = (T)s.omega; a.fuel[d] = (T)s.fuel; a.px[d] = (T)s.px; a.py[d] = (T)s.py;
+    a.total[d] = (T)s.total; a.status[d] = (uint8_t)s.status; a.steps[d] = s.steps;
+    if constexpr (kEpisode) a.episode[d] = s.episode;
+}
+
+// Lane d's pair of the notebook reward's two-frame distance history, hist [2][n]
+// (policy_rollout.hip, reinforce_fused.hip; ac_fused.hip moves the pair by hand).
+__device__ __forceinline__ void load_hist(const double* hist, int64_t n, int64_t d, double& h0, double& h1) {
+    h0 = hist[d];
+    h1 = hist[n + d];
+}
+
+__device__ __forceinline__ void store_hist(double* hist, int64_t n, int64_t d, double h0, double h1) {
+    hist[d] = h0;
+    hist[n + d] = h1;
 }
 
 // Writes a block's [rows, 15] observation tile from LDS to global memory as

@@ -153,10 +153,7 @@ __global__ __launch_bounds__(kThreads) void policy_eval_kernel(const float* __re
     const int64_t env = a.env_id_base + d;
 
     Lane s;
-    s.x = a.x[d]; s.y = a.y[d]; s.vx = a.vx[d]; s.vy = a.vy[d]; s.angle = a.angle[d]; s.omega = a.omega[d];
-    s.fuel = a.fuel[d]; s.px = a.px[d]; s.py = a.py[d]; s.total = a.total[d];
-    s.status = a.status[d]; s.steps = a.steps[d];
-    s.episode = 0;  // (no re-spawn here: the lane's episode counter is neither read nor written)
+    load_lane<false>(a, d, s);  // (no re-spawn here: the lane's episode counter is neither read nor written)
     double prev = ppo ? p.prev_dist[d] : 0.0;  // prev_state.distance_to_platform: the state the actor saw
     float x[8];
 #pragma unroll
@@ -240,9 +237,7 @@ __global__ __launch_bounds__(kThreads) void policy_eval_kernel(const float* __re
 
     if (p.obs_final) prl::store_rows<kSplit>(slice, x, c, h, rows, p.obs_final + d0 * DD_OBS_DIM, p.final_aligned);
     if (writer) {
-        a.x[d] = (T)s.x; a.y[d] = (T)s.y; a.vx[d] = (T)s.vx; a.vy[d] = (T)s.vy; a.angle[d] = (T)s.angle;
-        a.omega[d] = (T)s.omega; a.fuel[d] = (T)s.fuel; a.px[d] = (T)s.px; a.py[d] = (T)s.py;
-        a.total[d] = (T)s.total; a.status[d] = (uint8_t)s.status; a.steps[d] = s.steps;
+        store_lane<false>(a, d, s);
         if (ppo) p.prev_dist[d] = prev;
         p.ep_return[d] = ep.ret;
         p.ep_steps[d] = ep.steps;

@@ -144,11 +144,9 @@ __global__ __launch_bounds__(kThreads) void policy_rollout_kernel(const float* _
     const int64_t env = a.env_id_base + d;
 
     Lane s;
-    s.x = a.x[d]; s.y = a.y[d]; s.vx = a.vx[d]; s.vy = a.vy[d]; s.angle = a.angle[d]; s.omega = a.omega[d];
-    s.fuel = a.fuel[d]; s.px = a.px[d]; s.py = a.py[d]; s.total = a.total[d];
-    s.status = a.status[d]; s.steps = a.steps[d]; s.episode = a.episode[d];
+    load_lane(a, d, s);
     double h0 = 0.0, h1 = 0.0;  // the notebook reward's two-frame distance history
-    if (ppo) { h0 = p.shaped_hist[d]; h1 = p.shaped_hist[p.n + d]; }
+    if (ppo) load_hist(p.shaped_hist, p.n, d, h0, h1);
     float x[8];
 #pragma unroll
     for (int q = 0; q < 8; ++q) {
@@ -221,30 +219,8 @@ __global__ __launch_bounds__(kThreads) void policy_rollout_kernel(const float* _
         if (shaped) {  // dd_step's notebook path (PPO: the history in h0 / h1)
             double v[13];
             observe_values<kGuard, true>(k, s, v);  // the notebook reward's doubles: exact quotients
-            double sr = 0.0;
-            bool sd;
-            if (sw.auto_reset && was_done) {  // re-spawned: prev_state None
-                h0 = v[9];
-                h1 = __builtin_nan("");
-                sd = false;
-            } else if (was_done) {
-                sd = true;
-            } else {
-                if (ppo) {
-                    const bool odd = (s.steps & 1) != 0;
-                    sr = notebook_reward(v, s.status, odd ? h1 : h0);
-                    h1 = odd ? v[9] : h1;
-                    h0 = odd ? h0 : v[9];
-                } else {
-                    sr = reinforce_reward(v, s.status);
-                }
-                sd = (s.status & DD_ST_DONE) != 0;
-                if (p.max_steps > 0 && s.steps >= p.max_steps) {  // the collection loops' timeout
-                    sr = (s.status & DD_ST_LANDED) ? sr : sr - 500;
-                    sd = true;
-                    s.status |= DD_ST_DONE;
-                }
-            }
+            double sr;
+            const bool sd = shaped_tail(v, s, ppo, was_done, sw.auto_reset && was_done, p.max_steps, h0, h1, sr);
             if constexpr (kEval) {
                 ep_rew = (T)sr;
                 ep_done = sd;
@@ -282,10 +258,8 @@ __global__ __launch_bounds__(kThreads) void policy_rollout_kernel(const float* _
 
     if (p.obs_final) store_rows<kSplit>(slice, x, c, h, rows, p.obs_final + d0 * DD_OBS_DIM, p.final_aligned);
     if (writer) {
-        a.x[d] = (T)s.x; a.y[d] = (T)s.y; a.vx[d] = (T)s.vx; a.vy[d] = (T)s.vy; a.angle[d] = (T)s.angle;
-        a.omega[d] = (T)s.omega; a.fuel[d] = (T)s.fuel; a.px[d] = (T)s.px; a.py[d] = (T)s.py;
-        a.total[d] = (T)s.total; a.status[d] = (uint8_t)s.status; a.steps[d] = s.steps; a.episode[d] = s.episode;
-        if (ppo) { p.shaped_hist[d] = h0; p.shaped_hist[p.n + d] = h1; }
+        store_lane(a, d, s);
+        if (ppo) store_hist(p.shaped_hist, p.n, d, h0, h1);
         if constexpr (kEval) {
             if (stats) {
                 p.ep_return[d] = ep_return;

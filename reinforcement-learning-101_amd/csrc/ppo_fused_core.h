@@ -4,7 +4,12 @@
 // which runs the same walk for every member of a population, so both leave the
 // same bits.  The phases after a step's head gradient (backward_norm,
 // clip_adamw, repack) are functions of their own: dd_actor_critic_train
-// (ac_fused.hip) runs them inside its frame loop.
+// (ac_fused.hip) runs them inside its frame loop, dd_reinforce_train
+// (reinforce_fused.hip) the last two after its own backward.  Both also take
+// load_image here, reinforce_fused.hip load_row, and all three member-table
+// entries (ppo_fused_population.hip, ac_fused.hip, reinforce_fused.hip) the
+// host section's clip_of, the check that no two owners share a buffer (Owned,
+// owned_of / owned_apart, shared_between_owners) and launch_with_table.
 //
 // learn<K, Rows> is parameterised on where a minibatch's rows come from:
 //   DirectRows  rows [first, first + rows) of the columns as the caller laid
@@ -31,6 +36,9 @@
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
+
+#include <algorithm>
+#include <vector>
 
 #include "action_bits.h"
 #include "adamw_core.h"
@@ -136,6 +144,23 @@ __device__ __forceinline__ V stat_sum(V v, V nothing, V* sh) {
     V mine = threadIdx.x == 0 ? partial : nothing;
     mine += nothing;  // part[t] + part[t + kBlock]
     return block_sum<V>(mine, sh);
+}
+
+// A network's packed image into LDS (all threads; a barrier follows at the caller).
+__device__ __forceinline__ void load_image(const float* packed, float* lds) {
+    f32x4* lds4 = reinterpret_cast<f32x4*>(lds);
+    const f32x4* src4 = reinterpret_cast<const f32x4*>(packed);
+    for (int j = threadIdx.x; j < mlp::kPacked / 4; j += kBlock) lds4[j] = src4[j];
+}
+
+// Layer 1's B operand of a [15] row for this lane half: the row's columns
+// 2q + h, zero past column 14 and for a dead row.
+__device__ __forceinline__ void load_row(const float* row, bool live, int h, float (&x)[8]) {
+#pragma unroll
+    for (int q = 0; q < 8; ++q) {
+        const int col = 2 * q + h;
+        x[q] = live && col < DD_OBS_DIM ? row[col] : 0.0f;
+    }
 }
 
 // ---- one step's phases after the head gradient is written ---------------------
@@ -260,11 +285,7 @@ __device__ __forceinline__ void learn(const Args& a, const Net& n, const Rows& s
             const double md = (double)rows;
 
             // ---- forward: the packed image into LDS, a wave per 32 rows --------------
-            {
-                f32x4* lds4 = reinterpret_cast<f32x4*>(lds);
-                const f32x4* src4 = reinterpret_cast<const f32x4*>(n.packed);
-                for (int j = tid; j < mlp::kPacked / 4; j += kBlock) lds4[j] = src4[j];
-            }
+            load_image(n.packed, lds);
             __syncthreads();
             if (wave * mlp::kCols < rows) {
                 const int d = wave * mlp::kCols + c;
@@ -356,7 +377,7 @@ __device__ __forceinline__ void total_of(double* logs, int64_t count, int64_t j,
                            logs[DD_PPO_ENTROPY * count + j], entropy_coef, value_coef);
 }
 
-// ---- host: what both entries refuse, and the kernels' view of one learner ----------
+// ---- host: what the entries refuse, the kernels' view of one learner, the member-table launch ----
 inline bool net_ok(const DDPpoFusedNet& n) {
     if (!n.params || !n.grads || !n.exp_avg || !n.exp_avg_sq || !n.state || !n.packed) return false;
     if ((reinterpret_cast<uintptr_t>(n.state) & 7u) || (reinterpret_cast<uintptr_t>(n.packed) & 15u)) return false;
@@ -367,6 +388,71 @@ inline Net net_of(const DDPpoFusedNet& n, char* workspace) {
     float* image = reinterpret_cast<float*>(workspace);
     return {n.params, n.grads, n.exp_avg, n.exp_avg_sq, n.state, n.packed, image, image + kPackedB,
             adamw::args_of(n.hyper), n.ln_eps};
+}
+
+// Whether clip_grad_norm_ runs for a max_grad_norm (a NaN one is refused by the entries).
+inline bool clip_of(double max_grad_norm) { return max_grad_norm > 0.0 && __builtin_isfinite(max_grad_norm); }
+
+// A buffer of a network, for the entries' check that no two owners share one.
+// The owner is the member where a member's own networks may overlap
+// (dd_ppo_update_population), or a number of the buffer's own where nothing
+// may (dd_actor_critic_train, dd_reinforce_train).
+struct Owned {
+    uintptr_t first, last;  // [first, last)
+    int32_t owner;
+};
+
+// The six buffers of a K-output network, all `owner`'s.
+inline void owned_of(const DDPpoFusedNet& n, int k, int32_t owner, std::vector<Owned>& out) {
+    const uintptr_t floats = (uintptr_t)adamw::params_of(k) * sizeof(float);
+    const float* flat[4] = {n.params, n.grads, n.exp_avg, n.exp_avg_sq};
+    for (const float* p : flat) out.push_back({(uintptr_t)p, (uintptr_t)p + floats, owner});
+    out.push_back({(uintptr_t)n.state, (uintptr_t)n.state + sizeof(DDAdamWState), owner});
+    out.push_back({(uintptr_t)n.packed, (uintptr_t)n.packed + (uintptr_t)mlp::kPacked * sizeof(float), owner});
+}
+
+// The same with an owner per buffer, counted on from `next`: any overlap is one between owners.
+inline void owned_apart(const DDPpoFusedNet& n, int k, int32_t& next, std::vector<Owned>& out) {
+    const size_t from = out.size();
+    owned_of(n, k, 0, out);
+    for (size_t i = from; i < out.size(); ++i) out[i].owner = next++;
+}
+
+// Whether buffers of two different owners overlap.
+inline bool shared_between_owners(std::vector<Owned>& v) {
+    std::sort(v.begin(), v.end(), [](const Owned& x, const Owned& y) { return x.first < y.first; });
+    // of the ranges seen so far: the furthest end, and the furthest end among the other owners' ranges
+    uintptr_t end1 = 0, end2 = 0;
+    int32_t owner1 = -1;
+    for (const Owned& r : v) {
+        if (r.owner != owner1 ? r.first < end1 : r.first < end2) return true;
+        if (r.owner == owner1) {
+            end1 = std::max(end1, r.last);
+        } else if (r.last > end1) {
+            end2 = end1;
+            end1 = r.last;
+            owner1 = r.owner;
+        } else {
+            end2 = std::max(end2, r.last);
+        }
+    }
+    return false;
+}
+
+// The tail of a member-table launch: the table into the head of the workspace
+// on the stream, then `blocks` workgroups of `kernel` with the fused LDS, each
+// reading its own entry.  Returns after the launch; the caller ends with finish().
+template <typename M, typename... P, typename... A>
+hipError_t launch_with_table(void (*kernel)(const M*, P...), const std::vector<M>& table, void* workspace,
+                             unsigned blocks, hipStream_t s, const A&... args) {
+    // from pageable memory the copy has left `table` when the call returns
+    hipError_t e = hipMemcpyAsync(workspace, table.data(), table.size() * sizeof(M), hipMemcpyHostToDevice, s);
+    if (e != hipSuccess) return e;
+    // the LDS exceeds the 64 KB default; the attribute is per device, so it is set on every launch
+    e = hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLds);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(kernel, dim3(blocks), dim3(kBlock), kLds, s, static_cast<const M*>(workspace), args...);
+    return hipSuccess;
 }
 
 // One learner's batch and coefficients.
@@ -418,7 +504,7 @@ inline Args args_of(const Learner& l, int32_t num_epochs, int64_t size, int64_t 
     a.entropy_coef = l.entropy_coef;
     a.value_coef = l.value_coef;
     a.max_norm = l.max_grad_norm;
-    a.clip = l.max_grad_norm > 0.0 && __builtin_isfinite(l.max_grad_norm);
+    a.clip = clip_of(l.max_grad_norm);
     a.logs = l.logs;
     return a;
 }

@@ -121,41 +121,6 @@ __global__ __launch_bounds__(kBlock) void population_total_kernel(const Member* 
     if (j < count) total_of(a.logs, count, j, a.entropy_coef, a.value_coef);
 }
 
-// A network buffer of a member, for the check that no two members share one.
-struct Owned {
-    uintptr_t first, last;  // [first, last)
-    int32_t member;
-};
-
-inline void owned_of(const DDPpoFusedNet& n, int k, int32_t member, std::vector<Owned>& out) {
-    const uintptr_t floats = (uintptr_t)adamw::params_of(k) * sizeof(float);
-    const float* flat[4] = {n.params, n.grads, n.exp_avg, n.exp_avg_sq};
-    for (const float* p : flat) out.push_back({(uintptr_t)p, (uintptr_t)p + floats, member});
-    out.push_back({(uintptr_t)n.state, (uintptr_t)n.state + sizeof(DDAdamWState), member});
-    out.push_back({(uintptr_t)n.packed, (uintptr_t)n.packed + (uintptr_t)mlp::kPacked * sizeof(float), member});
-}
-
-// Whether buffers of two different members overlap.
-inline bool shared_between_members(std::vector<Owned>& v) {
-    std::sort(v.begin(), v.end(), [](const Owned& x, const Owned& y) { return x.first < y.first; });
-    // of the ranges seen so far: the furthest end, and the furthest end among the other members' ranges
-    uintptr_t end1 = 0, end2 = 0;
-    int32_t member1 = -1;
-    for (const Owned& r : v) {
-        if (r.member != member1 ? r.first < end1 : r.first < end2) return true;
-        if (r.member == member1) {
-            end1 = std::max(end1, r.last);
-        } else if (r.last > end1) {
-            end2 = end1;
-            end1 = r.last;
-            member1 = r.member;
-        } else {
-            end2 = std::max(end2, r.last);
-        }
-    }
-    return false;
-}
-
 }  // namespace fused
 }  // namespace dd
 
@@ -196,19 +161,13 @@ int dd_ppo_update_population(const DDPpoPopulationIO* io, void* workspace, void*
         owned_of(mb.actor, 3, p, owned);
         owned_of(mb.critic, 1, p, owned);
     }
-    if (shared_between_members(owned)) return hipErrorInvalidValue;
+    if (shared_between_owners(owned)) return hipErrorInvalidValue;  // a member's own networks may share
 
     hipStream_t s = static_cast<hipStream_t>(stream);
-    // from pageable memory the copy has left `table` when the call returns
-    hipError_t e = hipMemcpyAsync(workspace, table.data(), (size_t)table_bytes(members), hipMemcpyHostToDevice, s);
+    const hipError_t e = launch_with_table(population_kernel, table, workspace, 2u * (unsigned)members, s, blocks);
     if (e != hipSuccess) return (int)e;
-    // the LDS exceeds the 64 KB default; the attribute is per device, so it is set on every launch
-    e = hipFuncSetAttribute((const void*)population_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLds);
-    if (e != hipSuccess) return (int)e;
-    const Member* device_table = static_cast<const Member*>(workspace);
-    hipLaunchKernelGGL(population_kernel, dim3(2u * (unsigned)members), dim3(dd::kBlock), kLds, s, device_table, blocks);
     hipLaunchKernelGGL(population_total_kernel, dim3((unsigned)dd::tiles_of(most), (unsigned)members),
-                       dim3(dd::kBlock), 0, s, device_table);
+                       dim3(dd::kBlock), 0, s, static_cast<const Member*>(workspace));
     return dd::finish();
 }
 

@@ -16,10 +16,11 @@
 //      (an LDS tile) go to the member's frame-major record, the forward
 //      (mlp_core.h mlp_body, a wave per 32 rows) and the Bernoulli draw
 //      (actor_sample, keys (seed; env id, step + f)), then the frame, thread k
-//      the member's lane k with its state in registers, exactly
-//      policy_rollout.hip's body for a sticky env: frame.h's frame, the reward
-//      stream (engine, PPO's calc_reward with its history, REINFORCE's), the
-//      timeout, quantize.  Action bits and the returned reward go to the record.
+//      the member's lane k with its state in registers (lane_io.h load_lane /
+//      store_lane), exactly policy_rollout.hip's frame for a sticky env:
+//      frame.h's frame, the reward stream (engine, or frame.h's shaped_tail:
+//      PPO's calc_reward with its history, REINFORCE's, the timeout), quantize.
+//      Action bits and the returned reward go to the record.
 //      Early stop.  The frame loop ends after the first frame in which every
 //      lane of the member was done BEFORE the frame.  Such a frame maps a done
 //      lane's stored (quantized) state to itself: frame.h's sticky path is
@@ -59,7 +60,6 @@
 // by __syncthreads(), never behind a const __restrict__ pointer, ordinary
 // vector stores).  The member table is uploaded into the head of the workspace
 // and only ever read.
-#include <algorithm>
 #include <vector>
 
 #include "frame.h"
@@ -70,12 +70,13 @@
 namespace dd {
 namespace rf {
 
-using fused::kLds;
 using fused::kNormAt;
 using fused::kRedAt;
 using fused::kRowFloats;
 using fused::kRowsAt;
 using fused::kTileRows;
+using fused::load_image;
+using fused::load_row;
 using fused::Net;
 using mlp::f32x4;
 using mlpbwd::kFinishBlocks;
@@ -161,22 +162,6 @@ struct Cells {
     __device__ __forceinline__ int64_t cell(int64_t row) const { return map[row]; }
 };
 
-// A network's packed image into LDS (all threads; a barrier follows at the caller).
-__device__ __forceinline__ void load_image(const float* packed, float* lds) {
-    f32x4* lds4 = reinterpret_cast<f32x4*>(lds);
-    const f32x4* src4 = reinterpret_cast<const f32x4*>(packed);
-    for (int j = threadIdx.x; j < mlp::kPacked / 4; j += kBlock) lds4[j] = src4[j];
-}
-
-// Layer 1's B operand of a [15] row for this lane half (zero past column 14 and for a dead row).
-__device__ __forceinline__ void load_row(const float* row, bool live, int h, float (&x)[8]) {
-#pragma unroll
-    for (int q = 0; q < 8; ++q) {
-        const int col = 2 * q + h;
-        x[q] = live && col < DD_OBS_DIM ? row[col] : 0.0f;
-    }
-}
-
 // The total over m rows of value(k) as a kStatBlocks-block launch forms it
 // (stat_sum_kernel, stat_dev_kernel, pg_rows_kernel): stat block sb, thread t
 // adds its rows sb kBlock + t + j kStatBlocks kBlock in order from 0.0, the
@@ -247,12 +232,10 @@ __global__ __launch_bounds__(kBlock) void train_kernel(const Member* __restrict_
 
     // ---- 1. collect ---------------------------------------------------------------------
     Lane s;
-    s.x = soa.x[d]; s.y = soa.y[d]; s.vx = soa.vx[d]; s.vy = soa.vy[d]; s.angle = soa.angle[d];
-    s.omega = soa.omega[d]; s.fuel = soa.fuel[d]; s.px = soa.px[d]; s.py = soa.py[d]; s.total = soa.total[d];
-    s.status = soa.status[d]; s.steps = soa.steps[d]; s.episode = soa.episode[d];
+    load_lane(soa, d, s);
     s.speed = 0.0; s.dist = 0.0;
     double h0 = 0.0, h1 = 0.0;  // the notebook reward's two-frame distance history
-    if (ppo) { h0 = a.shaped_hist[d]; h1 = a.shaped_hist[a.n + d]; }
+    if (ppo) load_hist(a.shaped_hist, a.n, d, h0, h1);
     load_image(actor.packed, lds);
     for (int idx = tid; idx < L * DD_OBS_DIM; idx += kBlock) tile[idx] = obs[idx];
     __syncthreads();  // the image and the tile are written
@@ -293,31 +276,12 @@ __global__ __launch_bounds__(kBlock) void train_kernel(const Member* __restrict_
             }
             float reward_f;
             bool done_f;
-            if (shaped) {  // policy_rollout.hip's notebook path on a sticky env
+            if (shaped) {  // frame.h's shaped tail on a sticky env: never re-spawned
                 double v[13];
                 observe_values<false, true>(k, s, v);  // the notebook reward's doubles: exact quotients
-                double sr = 0.0;
-                bool sd;
-                if (was_done) {
-                    sd = true;
-                } else {
-                    if (ppo) {
-                        const bool odd = (s.steps & 1) != 0;
-                        sr = notebook_reward(v, s.status, odd ? h1 : h0);
-                        h1 = odd ? v[9] : h1;
-                        h0 = odd ? h0 : v[9];
-                    } else {
-                        sr = reinforce_reward(v, s.status);
-                    }
-                    sd = (s.status & DD_ST_DONE) != 0;
-                    if (a.max_steps > 0 && s.steps >= a.max_steps) {  // the collection loops' timeout
-                        sr = (s.status & DD_ST_LANDED) ? sr : sr - 500;
-                        sd = true;
-                        s.status |= DD_ST_DONE;
-                    }
-                }
+                double sr;
+                done_f = shaped_tail(v, s, ppo, was_done, false, a.max_steps, h0, h1, sr);
                 reward_f = (float)sr;
-                done_f = sd;
             } else {
                 reward_f = (float)reward;
                 done_f = (s.status & DD_ST_DONE) != 0;
@@ -337,11 +301,8 @@ __global__ __launch_bounds__(kBlock) void train_kernel(const Member* __restrict_
         if (__syncthreads_and(was_done ? 1 : 0)) break;  // the tile is written; see "Early stop" above
     }
     if (mine) {
-        soa.x[d] = (float)s.x; soa.y[d] = (float)s.y; soa.vx[d] = (float)s.vx; soa.vy[d] = (float)s.vy;
-        soa.angle[d] = (float)s.angle; soa.omega[d] = (float)s.omega; soa.fuel[d] = (float)s.fuel;
-        soa.px[d] = (float)s.px; soa.py[d] = (float)s.py; soa.total[d] = (float)s.total;
-        soa.status[d] = (uint8_t)s.status; soa.steps[d] = s.steps; soa.episode[d] = s.episode;
-        if (ppo) { a.shaped_hist[d] = h0; a.shaped_hist[a.n + d] = h1; }
+        store_lane(soa, d, s);
+        if (ppo) store_hist(a.shaped_hist, a.n, d, h0, h1);
     }
     for (int idx = tid; idx < L * DD_OBS_DIM; idx += kBlock) obs[idx] = tile[idx];
 
@@ -469,29 +430,6 @@ __global__ __launch_bounds__(kBlock) void train_kernel(const Member* __restrict_
     }
 }
 
-// A network buffer of a member, for the check that no two members share one.
-struct Owned {
-    uintptr_t first, last;  // [first, last)
-};
-
-inline void owned_of(const DDPpoFusedNet& n, std::vector<Owned>& out) {
-    const uintptr_t floats = (uintptr_t)kCount * sizeof(float);
-    const float* flat[4] = {n.params, n.grads, n.exp_avg, n.exp_avg_sq};
-    for (const float* q : flat) out.push_back({(uintptr_t)q, (uintptr_t)q + floats});
-    out.push_back({(uintptr_t)n.state, (uintptr_t)n.state + sizeof(DDAdamWState)});
-    out.push_back({(uintptr_t)n.packed, (uintptr_t)n.packed + (uintptr_t)mlp::kPacked * sizeof(float)});
-}
-
-inline bool any_overlap(std::vector<Owned>& v) {
-    std::sort(v.begin(), v.end(), [](const Owned& x, const Owned& y) { return x.first < y.first; });
-    uintptr_t end = 0;
-    for (const Owned& r : v) {
-        if (r.first < end) return true;
-        end = std::max(end, r.last);
-    }
-    return false;
-}
-
 inline bool shape_ok(int32_t members, int64_t lanes, int32_t max_steps) {
     return members >= 1 && lanes >= 1 && lanes <= DD_PPO_FUSED_ROWS && max_steps >= 1 &&
            lanes * (int64_t)max_steps <= DD_REINFORCE_MAX_CELLS;
@@ -525,8 +463,9 @@ int dd_reinforce_train(const DDConfig* cfg, const DDState* st, const DDReinforce
     const int64_t member_bytes = layout_of(io->lanes_per_member * (int64_t)io->max_steps).total;
     char* blocks = static_cast<char*>(workspace) + table_bytes(members);
     std::vector<Member> table((size_t)members);
-    std::vector<Owned> owned;
+    std::vector<dd::fused::Owned> owned;  // every buffer its own owner: no two may overlap
     owned.reserve((size_t)members * 6);
+    int32_t owner = 0;
     for (int32_t q = 0; q < members; ++q) {
         const DDReinforceMember& m = io->table[q];
         if (!dd::fused::net_ok(m.actor)) return hipErrorInvalidValue;
@@ -535,11 +474,11 @@ int dd_reinforce_train(const DDConfig* cfg, const DDState* st, const DDReinforce
         t.net = dd::fused::net_of(m.actor, blocks + (int64_t)q * member_bytes);
         t.gamma = m.gamma;
         t.max_norm = m.max_grad_norm;
-        t.clip = m.max_grad_norm > 0.0 && __builtin_isfinite(m.max_grad_norm) ? 1 : 0;
+        t.clip = dd::fused::clip_of(m.max_grad_norm) ? 1 : 0;
         t._pad = 0;
-        owned_of(m.actor, owned);
+        dd::fused::owned_apart(m.actor, 3, owner, owned);
     }
-    if (any_overlap(owned)) return hipErrorInvalidValue;
+    if (dd::fused::shared_between_owners(owned)) return hipErrorInvalidValue;
 
     Args a{};
     a.k = dd::make_consts(*cfg);
@@ -567,19 +506,10 @@ int dd_reinforce_train(const DDConfig* cfg, const DDState* st, const DDReinforce
     const bool ref = dd::uses_reference_physics(*cfg);
 
     hipStream_t s = static_cast<hipStream_t>(stream);
-    // from pageable memory the copy has left `table` when the call returns
-    hipError_t e = hipMemcpyAsync(workspace, table.data(), (size_t)table_bytes(members), hipMemcpyHostToDevice, s);
-    if (e != hipSuccess) return (int)e;
-    const Member* device_table = static_cast<const Member*>(workspace);
     return dd::with_bool(ref, [&](auto r) {
-        constexpr bool kRef = decltype(r)::value;
-        // the LDS exceeds the 64 KB default; the attribute is per device, so it is set on every launch
-        const hipError_t err = hipFuncSetAttribute((const void*)train_kernel<kRef>,
-                                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLds);
-        if (err != hipSuccess) return (int)err;
-        hipLaunchKernelGGL(train_kernel<kRef>, dim3((unsigned)members), dim3(dd::kBlock), kLds, s, device_table, blocks,
-                           a, soa);
-        return dd::finish();
+        const hipError_t e = dd::fused::launch_with_table(train_kernel<decltype(r)::value>, table, workspace,
+                                                          (unsigned)members, s, blocks, a, soa);
+        return e != hipSuccess ? (int)e : dd::finish();
     });
 }
 

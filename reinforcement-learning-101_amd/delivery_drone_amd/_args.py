@@ -99,6 +99,53 @@ def clip_norm(max_norm) -> float:
     return float(max_norm)
 
 
+def per_member(name: str, value, members: int) -> list:
+    """A scalar for every member, or one value per member."""
+    if isinstance(value, (tuple, list)):
+        if len(value) != members:
+            raise ValueError(f"{name}: {len(value)} values for {members} members")
+        return list(value)
+    return [value] * members
+
+
+def member_scalars(members: int, *triples) -> list:
+    """A population call's per-member scalars: ``(name, value, check)`` triples
+    in, ``value`` a scalar or one per member; out, for every member the tuple of
+    its ``check(value)`` in the triples' order.  A refusal names the member."""
+    per = [per_member(name, value, members) for name, value, _ in triples]
+    scalars = []
+    for p in range(members):
+        try:
+            scalars.append(tuple(check(values[p]) for (_, _, check), values in zip(triples, per)))
+        except ValueError as exc:
+            raise ValueError(f"member {p}: {exc}") from None
+    return scalars
+
+
+def fused_env_lanes(env, pop, own_check) -> int:
+    """What a fused training launch needs of ``env``: the lanes per member of
+    ``pop``.  ``own_check(env)`` is the caller's own refusal, made between the
+    checks of the env itself and those of its lanes."""
+    from .vec_env import VecDroneEnv  # vec_env imports this module
+    if not isinstance(env, VecDroneEnv):
+        raise ValueError("env must be a VecDroneEnv")
+    if env.device != pop.device:
+        raise ValueError(f"the env is on {env.device}, the learners on {pop.device}")
+    if env.precision != "f32":
+        raise ValueError(f"the fused training loop steps precision='f32' envs only, this one is {env.precision!r}")
+    if env.ping_pong:
+        raise ValueError("the fused training loop steps an env in place: ping_pong=True is not supported")
+    own_check(env)
+    members, n = len(pop), env.num_envs
+    lanes = n // members
+    if lanes * members != n or lanes < 1:
+        raise ValueError(f"{n} lanes do not split into {members} equal groups, one per member")
+    if lanes > abi.DD_PPO_FUSED_ROWS:
+        raise ValueError(f"member 0: {lanes} lanes per member; the fused training loop takes at most "
+                         f"{abi.DD_PPO_FUSED_ROWS} (one row tile of the backward)")
+    return lanes
+
+
 def check_out(t, shape, dtype, dev, what) -> None:
     """A caller's output buffer.  ``what`` opens the message as the call site
     words it ("out must be a contiguous float32 tensor")."""

@@ -14,15 +14,15 @@ L)`` of one env.  Both leave the bits of the loop of launches
 from __future__ import annotations
 
 import ctypes
+from functools import partial
 from typing import NamedTuple, Optional
 
 import torch
 
-from . import _args, abi, adamw, population
-from .adamw import AdamW, FUSED_MAX_ROWS
+from . import _args, abi, adamw
+from .adamw import AdamW
 from .policy import MlpNet
 from .population import LearnerPopulation
-from .vec_env import VecDroneEnv
 
 __all__ = ["ActorCriticRun", "actor_critic_train", "actor_critic_train_population", "AC_LOG_KEYS"]
 
@@ -47,26 +47,9 @@ class ActorCriticRun(NamedTuple):
         return self.logs[AC_LOG_KEYS.index(key)]
 
 
-def _check_env(env, pop: LearnerPopulation) -> int:
-    """What the launch needs of ``env``: the lanes per member."""
-    if not isinstance(env, VecDroneEnv):
-        raise ValueError("env must be a VecDroneEnv")
-    if env.device != pop.device:
-        raise ValueError(f"the env is on {env.device}, the learners on {pop.device}")
-    if env.precision != "f32":
-        raise ValueError(f"the fused training loop steps precision='f32' envs only, this one is {env.precision!r}")
-    if env.ping_pong:
-        raise ValueError("the fused training loop steps an env in place: ping_pong=True is not supported")
+def _check_reward_mode(env) -> None:
     if env.reward_mode not in ("engine", "notebook"):
         raise ValueError(f"reward_mode must be 'engine' or 'notebook', this env has {env.reward_mode!r}")
-    members, n = len(pop), env.num_envs
-    lanes = n // members
-    if lanes * members != n or lanes < 1:
-        raise ValueError(f"{n} lanes do not split into {members} equal groups, one per member")
-    if lanes > FUSED_MAX_ROWS:
-        raise ValueError(f"member 0: {lanes} lanes per member; the fused training loop takes at most {FUSED_MAX_ROWS} "
-                         "(one row tile of the backward)")
-    return lanes
 
 
 def actor_critic_train_population(env, pop: LearnerPopulation, frames: int, *, seed: int = 0, step: int = 0,
@@ -109,20 +92,14 @@ def actor_critic_train_population(env, pop: LearnerPopulation, frames: int, *, s
     from host memory at every call)."""
     if not isinstance(pop, LearnerPopulation):
         raise ValueError("pop must be a LearnerPopulation")
-    lanes = _check_env(env, pop)
+    lanes = _args.fused_env_lanes(env, pop, _check_reward_mode)
     members, n, dev = len(pop), env.num_envs, pop.device
     frames = int(frames)
     if frames < 1:
         raise ValueError(f"frames must be at least 1, got {frames}")
-    per = {name: population._per_member(name, value, members)
-           for name, value in (("gamma", gamma), ("value_reg", value_reg), ("max_grad_norm", max_grad_norm))}
-    scalars = []
-    for p in range(members):
-        try:
-            scalars.append((_args.finite("gamma", per["gamma"][p]), _args.finite("value_reg", per["value_reg"][p]),
-                            _args.clip_norm(per["max_grad_norm"][p])))
-        except ValueError as exc:
-            raise ValueError(f"member {p}: {exc}") from None
+    scalars = _args.member_scalars(members, ("gamma", gamma, partial(_args.finite, "gamma")),
+                                   ("value_reg", value_reg, partial(_args.finite, "value_reg")),
+                                   ("max_grad_norm", max_grad_norm, _args.clip_norm))
     active0 = _args.active_mask(active0, n, dev)
 
     table = (abi.DDActorCriticMember * members)()
@@ -146,9 +123,7 @@ def actor_critic_train_population(env, pop: LearnerPopulation, frames: int, *, s
     abi.check(pop._lib.dd_actor_critic_train(ctypes.byref(env._cfg), ctypes.byref(env._state), ctypes.byref(io), n,
                                              pop._workspace.data_ptr(), _args.stream_ptr(dev)),
               "dd_actor_critic_train")
-    env._dist = env._speed = None
-    env._obs_current = True  # the observation after the last frame
-    env._last_actions = None
+    env._trained_in_place()
     return ActorCriticRun(logs, env.obs, done_last, rec_reward, rec_done.view(torch.bool) if record else None)
 
 
@@ -160,12 +135,6 @@ def actor_critic_train(env, actor: MlpNet, critic: MlpNet, actor_opt: AdamW, cri
     one launch, ``logs`` ``[len(AC_LOG_KEYS), frames, 1]``.  The population of
     one, with its workspace, is built on the first call and kept on
     ``actor_opt``."""
-    pop = getattr(actor_opt, "_ac_pop", None) if isinstance(actor_opt, AdamW) else None
-    if pop is None or tuple(pop[0]) != (actor, critic, actor_opt, critic_opt):
-        try:
-            pop = LearnerPopulation([(actor, critic, actor_opt, critic_opt)])
-        except ValueError as exc:
-            raise ValueError(str(exc).replace("member 0: ", "", 1)) from None
-        actor_opt._ac_pop = pop
+    pop = LearnerPopulation._of_one(actor_opt, "_ac_pop", (actor, critic, actor_opt, critic_opt))
     return actor_critic_train_population(env, pop, frames, seed=seed, step=step, gamma=gamma, value_reg=value_reg,
                                          max_grad_norm=max_grad_norm, active0=active0, record=record)

@@ -30,60 +30,50 @@ from .train_batch import PpoBatch, ppo_batch
 __all__ = ["LearnerPopulation", "ReinforcePopulation", "ppo_update_population", "collect_ppo_population"]
 
 
-class LearnerPopulation(Sequence):
-    """The learners of a sweep: ``members`` is a non-empty sequence of
-    ``(actor, critic, actor_opt, critic_opt)``, each what :func:`ppo_update`
-    takes (``actor_opt`` optimizes ``actor``, ``critic_opt`` ``critic``), all
-    ``compute="f32"``, on one device and of one library; no network may appear
-    twice.  Anything else raises ``ValueError`` naming the member.
-
-    ``actors`` is the :class:`ActorPopulation` of the members' actors, built
-    once: an update rewrites each packed image in place, so the next
-    ``env.policy_rollout(pop.actors, ...)`` runs the new weights.  The
-    population owns the update's workspace (the descriptor table, and per
-    workgroup the backward's weight images, the head gradient and the row
-    stage), allocated here once and sized for
-    :func:`actor_critic_train_population`'s launch as well."""
+class _Population(Sequence):
+    """What the populations share: ``members`` as a tuple of tuples, none
+    empty; every network of a member (``_member_nets``, the subclass's check of
+    the member's shape) ``compute="f32"`` and in the population once; one
+    device and one library; ``actors``, the members' first networks."""
 
     def __init__(self, members):
         members = tuple(tuple(m) if isinstance(m, (tuple, list)) else m for m in members)
         if not members:
-            raise ValueError("LearnerPopulation needs at least one member")
-        seen = set()
+            raise ValueError(f"{type(self).__name__} needs at least one member")
+        seen, nets_of_members = set(), []
         for p, member in enumerate(members):
-            if not isinstance(member, tuple) or len(member) != 4:
-                raise ValueError(f"member {p}: expected (actor, critic, actor_opt, critic_opt)")
-            actor, critic, actor_opt, critic_opt = member
-            if not isinstance(actor, MlpNet) or not isinstance(critic, MlpNet):
-                raise ValueError(f"member {p}: the actor and the critic must be MlpNets")
-            if not isinstance(actor_opt, AdamW) or not isinstance(critic_opt, AdamW):
-                raise ValueError(f"member {p}: actor_opt and critic_opt must be AdamW optimizers")
-            if actor_opt.net is not actor or critic_opt.net is not critic:
-                raise ValueError(f"member {p}: actor_opt must optimize actor and critic_opt critic")
-            try:
-                _args.check_actor_critic(actor, critic)
-            except ValueError as exc:
-                raise ValueError(f"member {p}: {exc}") from None
-            for name, net in (("actor", actor), ("critic", critic)):
+            nets = self._member_nets(p, member)
+            for name, net in nets:
                 if net.compute != "f32":
                     raise ValueError(f"member {p}: a population update runs compute='f32' networks only, the {name} "
                                      f"is compute={net.compute!r}")
                 if id(net) in seen:
                     raise ValueError(f"member {p}: its {name} is in the population already")
                 seen.add(id(net))
+            nets_of_members.append([net for _, net in nets])
         self._members = members
-        self.device, self._lib = _one_device_and_library([(m[0], m[1]) for m in members])
+        self.device, self._lib = _one_device_and_library(nets_of_members)
         self.actors = ActorPopulation([m[0] for m in members])
-        # one workspace for either launch over the members: the PPO update's, or the actor-critic loop's
-        size = max(int(self._lib.dd_ppo_update_population_workspace(len(members))),
-                   int(self._lib.dd_actor_critic_train_workspace(len(members))))
-        self._workspace = torch.empty(size // 8, dtype=torch.int64, device=self.device)
 
     def __len__(self) -> int:
         return len(self._members)
 
     def __getitem__(self, p):
         return self._members[p]
+
+    @classmethod
+    def _of_one(cls, opt, attr: str, member: tuple):
+        """The population of the one learner ``member``, built on the first
+        call and kept on its optimizer ``opt`` as ``attr``; a refusal speaks
+        of the learner, not of "member 0"."""
+        pop = getattr(opt, attr, None) if isinstance(opt, AdamW) else None
+        if pop is None or tuple(pop[0]) != member:
+            try:
+                pop = cls([member])
+            except ValueError as exc:
+                raise ValueError(str(exc).replace("member 0: ", "", 1)) from None
+            setattr(opt, attr, pop)
+        return pop
 
 
 def _one_device_and_library(nets_of_members):
@@ -99,7 +89,47 @@ def _one_device_and_library(nets_of_members):
     return first.device, first._lib
 
 
-class ReinforcePopulation(Sequence):
+class LearnerPopulation(_Population):
+    """The learners of a sweep: ``members`` is a non-empty sequence of
+    ``(actor, critic, actor_opt, critic_opt)``, each what :func:`ppo_update`
+    takes (``actor_opt`` optimizes ``actor``, ``critic_opt`` ``critic``), all
+    ``compute="f32"``, on one device and of one library; no network may appear
+    twice.  Anything else raises ``ValueError`` naming the member.
+
+    ``actors`` is the :class:`ActorPopulation` of the members' actors, built
+    once: an update rewrites each packed image in place, so the next
+    ``env.policy_rollout(pop.actors, ...)`` runs the new weights.  The
+    population owns the update's workspace (the descriptor table, and per
+    workgroup the backward's weight images, the head gradient and the row
+    stage), allocated here once and sized for
+    :func:`actor_critic_train_population`'s launch as well."""
+
+    def __init__(self, members):
+        super().__init__(members)
+        # one workspace for either launch over the members: the PPO update's, or the actor-critic loop's
+        size = max(int(self._lib.dd_ppo_update_population_workspace(len(self))),
+                   int(self._lib.dd_actor_critic_train_workspace(len(self))))
+        self._workspace = torch.empty(size // 8, dtype=torch.int64, device=self.device)
+
+    @staticmethod
+    def _member_nets(p, member):
+        if not isinstance(member, tuple) or len(member) != 4:
+            raise ValueError(f"member {p}: expected (actor, critic, actor_opt, critic_opt)")
+        actor, critic, actor_opt, critic_opt = member
+        if not isinstance(actor, MlpNet) or not isinstance(critic, MlpNet):
+            raise ValueError(f"member {p}: the actor and the critic must be MlpNets")
+        if not isinstance(actor_opt, AdamW) or not isinstance(critic_opt, AdamW):
+            raise ValueError(f"member {p}: actor_opt and critic_opt must be AdamW optimizers")
+        if actor_opt.net is not actor or critic_opt.net is not critic:
+            raise ValueError(f"member {p}: actor_opt must optimize actor and critic_opt critic")
+        try:
+            _args.check_actor_critic(actor, critic)
+        except ValueError as exc:
+            raise ValueError(f"member {p}: {exc}") from None
+        return (("actor", actor), ("critic", critic))
+
+
+class ReinforcePopulation(_Population):
     """The learners of a REINFORCE sweep, which have no critic: ``members`` is
     a non-empty sequence of ``(actor, opt)``, each what
     :func:`reinforce_update` takes (``opt`` optimizes ``actor``), all
@@ -115,51 +145,27 @@ class ReinforcePopulation(Sequence):
     at the first call and grown when a later call needs more."""
 
     def __init__(self, members):
-        members = tuple(tuple(m) if isinstance(m, (tuple, list)) else m for m in members)
-        if not members:
-            raise ValueError("ReinforcePopulation needs at least one member")
-        seen = set()
-        for p, member in enumerate(members):
-            if not isinstance(member, tuple) or len(member) != 2:
-                raise ValueError(f"member {p}: expected (actor, opt)")
-            actor, opt = member
-            if not isinstance(actor, MlpNet) or actor.out_dim != 3:
-                raise ValueError(f"member {p}: the actor must be an MlpNet with out_dim 3")
-            if not isinstance(opt, AdamW):
-                raise ValueError(f"member {p}: opt must be an AdamW optimizer")
-            if opt.net is not actor:
-                raise ValueError(f"member {p}: opt must be the AdamW that optimizes actor")
-            if actor.compute != "f32":
-                raise ValueError(f"member {p}: a population update runs compute='f32' networks only, the actor "
-                                 f"is compute={actor.compute!r}")
-            if id(actor) in seen:
-                raise ValueError(f"member {p}: its actor is in the population already")
-            seen.add(id(actor))
-        self._members = members
-        self.device, self._lib = _one_device_and_library([(m[0],) for m in members])
-        self.actors = ActorPopulation([m[0] for m in members])
+        super().__init__(members)
         self._workspace = None
 
-    def __len__(self) -> int:
-        return len(self._members)
-
-    def __getitem__(self, p):
-        return self._members[p]
+    @staticmethod
+    def _member_nets(p, member):
+        if not isinstance(member, tuple) or len(member) != 2:
+            raise ValueError(f"member {p}: expected (actor, opt)")
+        actor, opt = member
+        if not isinstance(actor, MlpNet) or actor.out_dim != 3:
+            raise ValueError(f"member {p}: the actor must be an MlpNet with out_dim 3")
+        if not isinstance(opt, AdamW):
+            raise ValueError(f"member {p}: opt must be an AdamW optimizer")
+        if opt.net is not actor:
+            raise ValueError(f"member {p}: opt must be the AdamW that optimizes actor")
+        return (("actor", actor),)
 
     def _workspace_for(self, lanes: int, max_steps: int) -> torch.Tensor:
         size = int(self._lib.dd_reinforce_train_workspace(len(self), lanes, max_steps))
         if self._workspace is None or self._workspace.numel() * 8 < size:
             self._workspace = torch.empty((size + 7) // 8, dtype=torch.int64, device=self.device)
         return self._workspace
-
-
-def _per_member(name: str, value, members: int) -> list:
-    """A scalar for every member, or one value per member."""
-    if isinstance(value, (tuple, list)):
-        if len(value) != members:
-            raise ValueError(f"{name}: {len(value)} values for {members} members")
-        return list(value)
-    return [value] * members
 
 
 def ppo_update_population(pop: LearnerPopulation, batches, *, num_epochs: int = 4,
@@ -189,7 +195,7 @@ def ppo_update_population(pop: LearnerPopulation, batches, *, num_epochs: int = 
     batches = list(batches)
     if len(batches) != members:
         raise ValueError(f"batches: {len(batches)} batches for {members} members")
-    per = {name: _per_member(name, value, members)
+    per = {name: _args.per_member(name, value, members)
            for name, value in (("clip_epsilon", clip_epsilon), ("entropy_coef", entropy_coef),
                                ("value_coef", value_coef), ("max_grad_norm", max_grad_norm),
                                ("shuffle_seed", shuffle_seed))}

@@ -13,15 +13,15 @@ L)`` of one env.  Both leave the bits of the loop of launches.
 from __future__ import annotations
 
 import ctypes
+from functools import partial
 from typing import NamedTuple, Optional
 
 import torch
 
-from . import _args, abi, adamw, population
-from .adamw import AdamW, FUSED_MAX_ROWS
+from . import _args, abi, adamw
+from .adamw import AdamW
 from .policy import MlpNet
 from .population import ReinforcePopulation
-from .vec_env import VecDroneEnv
 
 __all__ = ["ReinforceRun", "reinforce_train", "reinforce_train_population", "REINFORCE_LOG_KEYS"]
 
@@ -50,26 +50,9 @@ class ReinforceRun(NamedTuple):
         return self.logs[REINFORCE_LOG_KEYS.index(key)]
 
 
-def _check_env(env, pop: ReinforcePopulation) -> int:
-    """What the launch needs of ``env``: the lanes per member."""
-    if not isinstance(env, VecDroneEnv):
-        raise ValueError("env must be a VecDroneEnv")
-    if env.device != pop.device:
-        raise ValueError(f"the env is on {env.device}, the learners on {pop.device}")
-    if env.precision != "f32":
-        raise ValueError(f"the fused training loop steps precision='f32' envs only, this one is {env.precision!r}")
-    if env.ping_pong:
-        raise ValueError("the fused training loop steps an env in place: ping_pong=True is not supported")
+def _check_sticky(env) -> None:
     if env.config.auto_reset:
         raise ValueError("REINFORCE collects one episode per lane: the env needs auto_reset=False")
-    members, n = len(pop), env.num_envs
-    lanes = n // members
-    if lanes * members != n or lanes < 1:
-        raise ValueError(f"{n} lanes do not split into {members} equal groups, one per member")
-    if lanes > FUSED_MAX_ROWS:
-        raise ValueError(f"member 0: {lanes} lanes per member; the fused training loop takes at most {FUSED_MAX_ROWS} "
-                         "(one row tile of the backward)")
-    return lanes
 
 
 def reinforce_train_population(env, pop: ReinforcePopulation, max_steps: int = 300, *, seed: int = 0, step: int = 0,
@@ -104,7 +87,7 @@ def reinforce_train_population(env, pop: ReinforcePopulation, max_steps: int = 3
     from host memory at every call)."""
     if not isinstance(pop, ReinforcePopulation):
         raise ValueError("pop must be a ReinforcePopulation")
-    lanes = _check_env(env, pop)
+    lanes = _args.fused_env_lanes(env, pop, _check_sticky)
     members, n, dev = len(pop), env.num_envs, pop.device
     max_steps = int(max_steps)
     if max_steps < 1:
@@ -112,14 +95,8 @@ def reinforce_train_population(env, pop: ReinforcePopulation, max_steps: int = 3
     if lanes * max_steps > abi.DD_REINFORCE_MAX_CELLS:
         raise ValueError(f"{lanes} lanes x {max_steps} frames per member; the fused training loop records at most "
                          f"{abi.DD_REINFORCE_MAX_CELLS} lane-frames")
-    per = {name: population._per_member(name, value, members)
-           for name, value in (("gamma", gamma), ("max_grad_norm", max_grad_norm))}
-    scalars = []
-    for p in range(members):
-        try:
-            scalars.append((_args.finite("gamma", per["gamma"][p]), _args.clip_norm(per["max_grad_norm"][p])))
-        except ValueError as exc:
-            raise ValueError(f"member {p}: {exc}") from None
+    scalars = _args.member_scalars(members, ("gamma", gamma, partial(_args.finite, "gamma")),
+                                   ("max_grad_norm", max_grad_norm, _args.clip_norm))
 
     table = (abi.DDReinforceMember * members)()
     for p, ((actor, opt), (g, norm)) in enumerate(zip(pop, scalars)):
@@ -143,9 +120,7 @@ def reinforce_train_population(env, pop: ReinforcePopulation, max_steps: int = 3
         ptr[0], ptr[1], ptr[2], ptr[3], logs.data_ptr())
     abi.check(pop._lib.dd_reinforce_train(ctypes.byref(env._cfg), ctypes.byref(env._state), ctypes.byref(io), n,
                                           workspace.data_ptr(), _args.stream_ptr(dev)), "dd_reinforce_train")
-    env._dist = env._speed = None
-    env._obs_current = True  # the observation after the last frame
-    env._last_actions = None
+    env._trained_in_place()
     return ReinforceRun(logs, lengths, ended.view(torch.bool), episode_return, env.obs, rec[0],
                         rec[1].view(torch.bool) if record else None, rec[2], rec[3])
 
@@ -157,12 +132,6 @@ def reinforce_train(env, actor: MlpNet, opt: AdamW, max_steps: int = 300, *, see
     lane of ``env`` (at most 128): one REINFORCE iteration, ``logs``
     ``[len(REINFORCE_LOG_KEYS), 1]``.  The population of one, with its
     workspace, is built on the first call and kept on ``opt``."""
-    pop = getattr(opt, "_reinforce_pop", None) if isinstance(opt, AdamW) else None
-    if pop is None or tuple(pop[0]) != (actor, opt):
-        try:
-            pop = ReinforcePopulation([(actor, opt)])
-        except ValueError as exc:
-            raise ValueError(str(exc).replace("member 0: ", "", 1)) from None
-        opt._reinforce_pop = pop
+    pop = ReinforcePopulation._of_one(opt, "_reinforce_pop", (actor, opt))
     return reinforce_train_population(env, pop, max_steps, seed=seed, step=step, gamma=gamma,
                                       max_grad_norm=max_grad_norm, normalize=normalize, record=record)

@@ -2,11 +2,15 @@
 (csrc/ppo_fused_population.hip): the header's declarations and abi.py's
 binding of them, the struct layouts against the C compiler, the workspace
 size, and every argument error, each returned before any HIP call (fake
-pointers throughout, no device present)."""
+pointers throughout, no device present).  One case, the last, passes every
+check and ends at the upload for lack of a device; it is not run where there
+is one."""
 import ctypes
 import os
 import re
 import subprocess
+
+import pytest
 
 from delivery_drone_amd import abi
 
@@ -140,3 +144,18 @@ def test_members_may_not_share_a_network_buffer():
             assert run({which: {name: mine + 16}}, at=2) == EINVAL, (which, name)     # inside it
     # a flat buffer that ends inside another member's
     assert run({"actor": dict(grads=other - 64)}, at=1) == EINVAL
+
+
+def test_a_members_own_networks_may_share_a_buffer():
+    """The owner rule from the other side: buffers of one member that overlap pass the check between members (the
+    call then fails like a good one, at the upload: no device here), while dd_actor_critic_train and
+    dd_reinforce_train refuse any overlap (their own files).  With a device the accepted calls would upload to the
+    fake workspace and launch, so the case runs only where there is none."""
+    if os.path.exists("/dev/kfd"):
+        pytest.skip("a GPU is present: an accepted call would launch on fake pointers")
+    good = run()
+    assert good != EINVAL  # every check passed; the runtime's error for the missing device
+    mine = 2 * STRIDE  # member 1's actor buffers start here
+    assert run({"critic": dict(grads=mine + (1 << 18))}, at=1) == good       # its actor's gradient buffer
+    assert run({"critic": dict(exp_avg=mine + (1 << 18) + 16)}, at=1) == good  # inside it
+    assert run({"critic": dict(grads=mine + (1 << 18))}, at=2) == EINVAL     # another member's: refused
