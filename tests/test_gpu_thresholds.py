@@ -25,7 +25,10 @@ tests), and under a config that moves every landing boundary off config.py's
 drone, margin 35, with wind), where the kernarg frame's near-boundary redo
 must follow the call's limits; tests/threshold_states.py places the states at
 the config's own boundaries.  The oracle alone shows the guards below hold
-for it (all states within 16.5 ulps; 28-31 % landed, 24-26 % crashed)."""
+for it (all states within 16.5 ulps; 28-31 % landed, 24-26 % crashed).
+The "policy" path's random actor leaves most lanes' boundaries (a state is
+placed for one action); the action-placed sweep of the fused loops lives in
+tests/test_gpu_threshold_paths.py."""
 import numpy as np
 import pytest
 import torch
