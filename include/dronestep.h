@@ -1496,6 +1496,108 @@ int64_t dd_reinforce_train_workspace(int32_t members, int64_t lanes, int32_t max
 int dd_reinforce_train(const DDConfig *cfg, const DDState *st, const DDReinforceIO *io, int64_t n, void *workspace,
                        void *stream);
 
+/* ---- PPO learners, one iteration in one launch (additions to ABI 13) ------------
+ * One iteration of Actor_Critic_PPO.ipynb's training cell for every member of a
+ * population.  Member g drives lanes [g L, (g + 1) L) of the batch `st` (L =
+ * lanes_per_member, 1 <= L <= DD_PPO_FUSED_ROWS, members L == n), which the
+ * caller has just reset (dd_reset), on a sticky env (cfg->auto_reset == 0: one
+ * episode per lane).  Exactly what these calls do on the member's lanes, bit
+ * for bit:
+ *   dd_policy_rollout of the actor for max_steps frames, as dd_reinforce_train
+ *     runs it (the same reward streams, timeout and early stop), its log-probs
+ *     kept as the batch's old log-probs
+ *   dd_batch_plan, dd_batch_gather, dd_mlp_forward of the critic on the M rows
+ *     (each lane's first episode; lanes ascending, a lane's rows in frame order)
+ *     and on the lanes' final observation (the bootstrap of a lane whose episode
+ *     did not end; 0 for one that did), dd_batch_advantages (DD_BATCH_GAE with
+ *     gamma and lambda, returns = advantages + values) and dd_batch_normalize
+ *   num_epochs epochs of PPO steps with the member's coefficients:
+ *     minibatch_size = B in [1, DD_PPO_FUSED_ROWS]: dd_ppo_update_fused's steps
+ *       on the rows perm(i min(B, M) + k; M, shuffle_seed, shuffle_epoch + e),
+ *       the tail shorter than B a step of its own unless drop_last (a member
+ *       with M < B and drop_last takes no step);
+ *     minibatch_size = 0: one step per epoch on all M rows in batch order:
+ *       dd_ppo_update_fused's for M <= DD_PPO_FUSED_ROWS; above that
+ *       dd_mlp_evaluate_actions / dd_mlp_forward, dd_ppo_losses with both
+ *       gradients, dd_mlp_backward (max_norm = max_grad_norm) and dd_adamw_step
+ *       of the actor and of the critic.
+ * One persistent kernel of `members` 256-thread workgroups, one per member,
+ * which runs both networks; no workgroup waits on another.  The batch's rows are
+ * read in place in a frame-major record of the member's frames.
+ * DD_MLP_F32 networks and DD_F32 state storage only.
+ * obs [n][15]: in, the current observation; out, the last frame's.  The state
+ * arrays and shaped_hist are left as the rollout leaves them.
+ * logs: [DD_PPO_FUSED_LOGS][num_epochs][steps][members] doubles, the rows of
+ * dd_ppo_update_fused; steps is 1 for minibatch_size 0, else ceil(L max_steps /
+ * minibatch_size), the most a member can take: the entries of the steps a member
+ * does not take are NaN.  batch_logs: [DD_PT_BATCH_LOGS][members] doubles: M,
+ * the mean and the unbiased std of the member's raw advantages (NaN for M < 2).
+ * lengths / ended / episode_return [n]: dd_batch_plan's and
+ * dd_batch_advantages' per lane; landed [n]: whether the lane's drone landed.
+ * record_reward (float) / record_done [max_steps][n], both or neither, and
+ * record_values / record_returns / record_advantages [max_steps][n], all or
+ * none: each lane's rows at their frames, zeros after its episode.
+ * The members' descriptors are a host array, copied into the head of the
+ * workspace on the stream as dd_ppo_update_population does; not for stream
+ * capture.  Nothing is read back.
+ * workspace: dd_ppo_train_workspace(members, lanes, max_steps) bytes, 16-byte
+ * aligned: linear in members, and DD_PPO_TRAIN_CELL_BYTES per cell of a member's
+ * lanes x max_steps cells (rounded up to a multiple of 4) on top of a fixed part
+ * per member; 0 for arguments the call refuses.
+ * hipErrorInvalidValue, before any HIP call: everything dd_reinforce_train
+ * refuses (with landed and batch_logs among the buffers that must be set, and
+ * the three-buffer record all or none); num_epochs < 1; minibatch_size outside
+ * {0} and [1, DD_PPO_FUSED_ROWS]; for any member, what dd_ppo_update_population
+ * refuses of a network, clip_epsilon, the two coefficients or max_grad_norm, a
+ * gamma or lambda that is not finite; network buffers that overlap (between
+ * members, or the actor's with the critic's). */
+#define DD_PPO_TRAIN_CELL_BYTES 124
+enum { DD_PT_ROWS = 0, DD_PT_ADV_MEAN = 1, DD_PT_ADV_STD = 2, DD_PT_BATCH_LOGS = 3 };
+typedef struct DDPpoTrainMember {
+    DDPpoFusedNet actor;         /* K = 3                                     */
+    DDPpoFusedNet critic;        /* K = 1                                     */
+    double gamma;                /* rounded to float32, as dd_gae does        */
+    double lambda;               /* gamma * lambda rounded to float32         */
+    double clip_epsilon;
+    double entropy_coef;
+    double value_coef;
+    double max_grad_norm;        /* <= 0 or inf: no clipping                  */
+    uint64_t shuffle_seed;
+} DDPpoTrainMember;
+
+typedef struct DDPpoTrainIO {
+    const DDPpoTrainMember *table;  /* host memory, [members]                 */
+    int32_t members;
+    int32_t max_steps;           /* frames collected at most                  */
+    int64_t lanes_per_member;
+    float *obs;                  /* [n][15]                                   */
+    double *shaped_hist;         /* [2][n]: PPO's reward; null otherwise      */
+    int32_t shaped_mode;         /* DD_SHAPED_PPO or DD_SHAPED_REINFORCE      */
+    int32_t env_max_steps;       /* the shaped rewards' timeout; <= 0: none   */
+    int32_t normalize;           /* nonzero: normalised advantages            */
+    int32_t num_epochs;
+    int32_t minibatch_size;      /* 0: the full batch                         */
+    int32_t drop_last;           /* nonzero: no tail minibatch                */
+    uint64_t shuffle_epoch;      /* epoch e of the call uses shuffle_epoch + e */
+    uint64_t seed;
+    int64_t step;
+    int32_t *lengths;            /* [n]                                       */
+    uint8_t *ended;              /* [n]                                       */
+    double *episode_return;      /* [n]                                       */
+    uint8_t *landed;             /* [n]                                       */
+    void *record_reward;         /* nullable float [max_steps][n]             */
+    uint8_t *record_done;        /* nullable [max_steps][n]                   */
+    float *record_values;        /* nullable [max_steps][n]                   */
+    float *record_returns;       /* nullable [max_steps][n]                   */
+    float *record_advantages;    /* nullable [max_steps][n]                   */
+    double *logs;                /* [DD_PPO_FUSED_LOGS][num_epochs][steps][members] */
+    double *batch_logs;          /* [DD_PT_BATCH_LOGS][members]               */
+} DDPpoTrainIO;
+
+int64_t dd_ppo_train_workspace(int32_t members, int64_t lanes, int32_t max_steps);
+int dd_ppo_train(const DDConfig *cfg, const DDState *st, const DDPpoTrainIO *io, int64_t n, void *workspace,
+                 void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -267,8 +267,17 @@ __device__ __forceinline__ void repack(const Net& n, const DDMlpParams& p, float
     __syncthreads();  // the image is written; the table is free again
 }
 
-template <int K, typename Rows>
-__device__ __forceinline__ void learn(const Args& a, const Net& n, const Rows& src, float* lds) {
+// Where learn writes its logs: a learner's own [DD_PPO_FUSED_LOGS][num_epochs]
+// [steps] block at a.logs.  dd_ppo_train gives a layout of its own.
+struct DenseLogs {
+    __device__ __forceinline__ double* entry(const Args& a, int epoch, int i) const {
+        return a.logs + (int64_t)epoch * a.steps + i;
+    }
+    __device__ __forceinline__ int64_t row(const Args& a) const { return (int64_t)a.num_epochs * a.steps; }
+};
+
+template <int K, typename Rows, typename Logs = DenseLogs>
+__device__ __forceinline__ void learn(const Args& a, const Net& n, const Rows& src, float* lds, Logs at_logs = {}) {
     constexpr bool kActor = K == 3;
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, h = lane >> 5, c = lane & 31;
     float* rowbuf = reinterpret_cast<float*>(reinterpret_cast<char*>(lds) + kRowsAt);
@@ -314,8 +323,8 @@ __device__ __forceinline__ void learn(const Args& a, const Net& n, const Rows& s
             __syncthreads();
 
             // ---- losses: thread k has row k ------------------------------------------
-            double* entry = a.logs + (int64_t)epoch * a.steps + i;
-            const int64_t log_row = (int64_t)a.num_epochs * a.steps;
+            double* entry = at_logs.entry(a, epoch, i);
+            const int64_t log_row = at_logs.row(a);
             if constexpr (kActor) {
                 Part acc = ppo::no_rows();
                 float rf = 0.0f;

@@ -11,7 +11,8 @@
 // workgroup waits on another (no flag, no spin, no grid barrier), so the grid
 // is `members` blocks and those past the card's CUs start when a CU is free.
 //
-//   1. Collect.  The actor's image is loaded into LDS once (the parameters do
+//   1. Collect (collect_core.h's collect_episodes, shared with dd_ppo_train).
+//      The actor's image is loaded into LDS once (the parameters do
 //      not change while collecting).  Per frame: the lanes' observation rows
 //      (an LDS tile) go to the member's frame-major record, the forward
 //      (mlp_core.h mlp_body, a wave per 32 rows) and the Bernoulli draw
@@ -62,20 +63,19 @@
 // and only ever read.
 #include <vector>
 
-#include "frame.h"
-#include "lane_io.h"
+#include "collect_core.h"
 #include "pg_core.h"
-#include "ppo_fused_core.h"
 
 namespace dd {
 namespace rf {
 
+using collect::Cells;
+using collect::rows_total;
+using collect::shape_ok;
 using fused::kNormAt;
 using fused::kRedAt;
-using fused::kRowFloats;
 using fused::kRowsAt;
 using fused::kTileRows;
-using fused::load_image;
 using fused::load_row;
 using fused::Net;
 using mlp::f32x4;
@@ -85,15 +85,6 @@ using mlpbwd::kPackedB;
 using mlpbwd::kPartStride;
 
 constexpr int kCount = adamw::params_of(3);
-
-// The lanes' current observation rows, behind the forward image.
-constexpr int kTileAt = mlp::kPacked;  // in floats
-static_assert((size_t)(kTileAt + kTileRows * DD_OBS_DIM) * sizeof(float) <= mlpbwd::kLdsB,
-              "the tile fits beside the image");
-// rows_total's partials and its block_sum scratch share the reductions' scratch.
-static_assert((size_t)(kStatBlocks + kBlock) * sizeof(double) <= kNormAt - kRedAt, "the partials fit");
-// the lanes' lengths sit in the per-row buffer
-static_assert(kTileRows * sizeof(int32_t) <= kRedAt - kRowsAt, "the lengths fit");
 
 // One member's workspace, in bytes from its start: the backward's weight
 // images, one partial gradient set, the double accumulators; then per cell of
@@ -138,9 +129,7 @@ static_assert(sizeof(Member) % 16 == 0, "the members' workspaces follow the tabl
 inline int64_t table_bytes(int64_t members) { return members * (int64_t)sizeof(Member); }
 
 struct Args {
-    Consts k;  // runtime constants (switches, spawn; physics when !kRef)
-    float* obs;
-    double* shaped_hist;  // [2][n] (PPO's reward) or null
+    collect::Env env;
     int32_t* lengths;
     uint8_t* ended;
     double* episode_return;
@@ -149,47 +138,9 @@ struct Args {
     float* record_returns;
     float* record_advantages;
     double* logs;
-    uint64_t seed;
-    int64_t step;
-    int64_t n;
     int64_t member_bytes;
-    int32_t lanes, members, frames, max_steps, shape, normalize;
+    int32_t members, normalize;
 };
-
-// Row r of the batch is cell map[r] of the record.
-struct Cells {
-    const int32_t* map;
-    __device__ __forceinline__ int64_t cell(int64_t row) const { return map[row]; }
-};
-
-// The total over m rows of value(k) as a kStatBlocks-block launch forms it
-// (stat_sum_kernel, stat_dev_kernel, pg_rows_kernel): stat block sb, thread t
-// adds its rows sb kBlock + t + j kStatBlocks kBlock in order from 0.0, the
-// block's 256 sums go through block_sum's tree (wave_block_sum: the same
-// additions), the partials through stat_total.  A block with no row has the
-// partial +0.  part: kStatBlocks doubles, sh: kBlock doubles (LDS).  Every
-// thread gets the total; ends with a barrier.
-template <typename F>
-__device__ __forceinline__ double rows_total(int64_t m, F value, double* part, double* sh) {
-    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-    const int64_t full = (m + kBlock - 1) / kBlock;
-    const int nb = (int)(full < kStatBlocks ? full : kStatBlocks);
-    for (int sb = nb + tid; sb < kStatBlocks; sb += kBlock) part[sb] = 0.0;
-    for (int sb = wave; sb < nb; sb += kBlock / 64) {
-        double x[4];
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            double s = 0.0;
-            for (int64_t k = (int64_t)sb * kBlock + 64 * q + lane; k < m; k += (int64_t)kStatBlocks * kBlock)
-                s += value(k);
-            x[q] = s;
-        }
-        const double t = wave_block_sum(x);
-        if (lane == 0) part[sb] = t;
-    }
-    __syncthreads();
-    return stat_total<double>(part, sh);
-}
 
 template <bool kRef>
 __global__ __launch_bounds__(kBlock) void train_kernel(const Member* __restrict__ table, char* workspace, Args a,
@@ -197,7 +148,6 @@ __global__ __launch_bounds__(kBlock) void train_kernel(const Member* __restrict_
     extern __shared__ f32x4 lds4[];
     float* lds = reinterpret_cast<float*>(lds4);
     float* rowbuf = reinterpret_cast<float*>(reinterpret_cast<char*>(lds) + kRowsAt);
-    float* tile = lds + kTileAt;
     double* part = reinterpret_cast<double*>(reinterpret_cast<char*>(lds) + kRedAt);
     double* redd = part + kStatBlocks;
     double* normp = reinterpret_cast<double*>(reinterpret_cast<char*>(lds) + kNormAt);
@@ -205,7 +155,8 @@ __global__ __launch_bounds__(kBlock) void train_kernel(const Member* __restrict_
     const int g = blockIdx.x;
     const Member mb = table[g];
     const Net& actor = mb.net;
-    const int L = a.lanes, T = a.frames;
+    const int L = a.env.lanes, T = a.env.frames;
+    const int64_t n = a.env.n;
     const int64_t d0 = (int64_t)g * L;
     const Layout lay = layout_of((int64_t)L * T);
     char* ws = workspace + (int64_t)g * a.member_bytes;
@@ -221,90 +172,16 @@ __global__ __launch_bounds__(kBlock) void train_kernel(const Member* __restrict_
     float* lpv = reinterpret_cast<float*>(ws + lay.lp);
     float* probv = reinterpret_cast<float*>(ws + lay.prob);
     float* head = reinterpret_cast<float*>(ws + lay.head);
-    float* obs = a.obs + d0 * DD_OBS_DIM;
     const bool mine = tid < L;  // thread k has the member's lane k
     const int64_t d = d0 + (mine ? tid : 0);
-    const DDConfig& sw = a.k.c;
-    const Consts& k = kRef ? kRefConsts : a.k;
-    const bool shaped = a.shape != kShapeNone;
-    const bool ppo = a.shape == kShapePpo;
     fused::Running run = fused::running_of(actor);
 
-    // ---- 1. collect ---------------------------------------------------------------------
-    Lane s;
-    load_lane(soa, d, s);
-    s.speed = 0.0; s.dist = 0.0;
-    double h0 = 0.0, h1 = 0.0;  // the notebook reward's two-frame distance history
-    if (ppo) load_hist(a.shaped_hist, a.n, d, h0, h1);
-    load_image(actor.packed, lds);
-    for (int idx = tid; idx < L * DD_OBS_DIM; idx += kBlock) tile[idx] = obs[idx];
-    __syncthreads();  // the image and the tile are written
-
-    int32_t len = T;  // the lane's first episode
-    bool ended = false;
-    double ep_return = 0.0;
-    for (int f = 0; f < T; ++f) {
-        float* frame_obs = rec_obs + (int64_t)f * L * DD_OBS_DIM;
-        for (int idx = tid; idx < L * DD_OBS_DIM; idx += kBlock) frame_obs[idx] = tile[idx];
-        if (wave * mlp::kCols < L) {
-            const int r = wave * mlp::kCols + c;
-            const bool live = r < L;
-            float x[8], z[3];
-            load_row(tile + (live ? r : 0) * DD_OBS_DIM, live, h, x);
-            mlp::mlp_body<3, false>(lds, lane, x, z);
-            if (live && h == 0) {
-                float prob[3], lp_drawn;
-                uint32_t bits;
-                mlp::actor_probs(z, prob);
-                mlp::actor_sample(prob, (uint64_t)(soa.env_id_base + d0 + r), (uint64_t)(a.step + f), a.seed, bits,
-                                  lp_drawn);
-                rowbuf[r * kRowFloats] = __uint_as_float(bits);
-            }
-        }
-        __syncthreads();  // the lanes' actions are written; the tile is read
-
-        bool was_done = true;
-        if (mine) {
-            const uint32_t act = __float_as_uint(rowbuf[tid * kRowFloats]);
-            was_done = (s.status & DD_ST_DONE) != 0;
-            double reward;
-            if (was_done) {  // sticky done (game_engine.py:107-111)
-                measure(s);
-                reward = 0.0;
-            } else {
-                reward = frame_checked<kRef, true>(k, sw, act, s);
-            }
-            float reward_f;
-            bool done_f;
-            if (shaped) {  // frame.h's shaped tail on a sticky env: never re-spawned
-                double v[13];
-                observe_values<false, true>(k, s, v);  // the notebook reward's doubles: exact quotients
-                double sr;
-                done_f = shaped_tail(v, s, ppo, was_done, false, a.max_steps, h0, h1, sr);
-                reward_f = (float)sr;
-            } else {
-                reward_f = (float)reward;
-                done_f = (s.status & DD_ST_DONE) != 0;
-            }
-            observe(k, s, tile + tid * DD_OBS_DIM);  // from the unrounded frame, like dd_step's obs
-            quantize<float, kRef>(s);
-            rec_bits[(int64_t)f * L + tid] = act;
-            rec_reward[(int64_t)f * L + tid] = reward_f;
-            if (!ended) {
-                ep_return += (double)reward_f;
-                if (done_f) {
-                    len = f + 1;
-                    ended = true;
-                }
-            }
-        }
-        if (__syncthreads_and(was_done ? 1 : 0)) break;  // the tile is written; see "Early stop" above
-    }
-    if (mine) {
-        store_lane(soa, d, s);
-        if (ppo) store_hist(a.shaped_hist, a.n, d, h0, h1);
-    }
-    for (int idx = tid; idx < L * DD_OBS_DIM; idx += kBlock) obs[idx] = tile[idx];
+    // ---- 1. collect (collect_core.h) ------------------------------------------------------
+    const collect::Episode ep =
+        collect::collect_episodes<kRef, false>(a.env, soa, g, actor.packed, lds, rec_obs, rec_bits, rec_reward, nullptr);
+    const int32_t len = ep.len;
+    const bool ended = ep.ended;
+    const double ep_return = ep.ep_return;
 
     // ---- 2. batch -----------------------------------------------------------------------
     int32_t* len_s = reinterpret_cast<int32_t*>(rowbuf);
@@ -330,8 +207,8 @@ __global__ __launch_bounds__(kBlock) void train_kernel(const Member* __restrict_
         }
         if (a.record_reward) {
             for (int32_t t = 0; t < T; ++t) {
-                a.record_reward[(int64_t)t * a.n + d] = t < len ? rec_reward[(int64_t)t * L + tid] : 0.0f;
-                a.record_done[(int64_t)t * a.n + d] = (uint8_t)(ended && t == len - 1 ? 1 : 0);
+                a.record_reward[(int64_t)t * n + d] = t < len ? rec_reward[(int64_t)t * L + tid] : 0.0f;
+                a.record_done[(int64_t)t * n + d] = (uint8_t)(ended && t == len - 1 ? 1 : 0);
             }
         }
     }
@@ -352,8 +229,8 @@ __global__ __launch_bounds__(kBlock) void train_kernel(const Member* __restrict_
     __syncthreads();  // the advantages are written
     if (mine && a.record_returns) {
         for (int32_t t = 0; t < T; ++t) {
-            a.record_returns[(int64_t)t * a.n + d] = t < len ? ret[off + t] : 0.0f;
-            a.record_advantages[(int64_t)t * a.n + d] = t < len ? adv[off + t] : 0.0f;
+            a.record_returns[(int64_t)t * n + d] = t < len ? ret[off + t] : 0.0f;
+            a.record_advantages[(int64_t)t * n + d] = t < len ? adv[off + t] : 0.0f;
         }
     }
 
@@ -430,11 +307,6 @@ __global__ __launch_bounds__(kBlock) void train_kernel(const Member* __restrict_
     }
 }
 
-inline bool shape_ok(int32_t members, int64_t lanes, int32_t max_steps) {
-    return members >= 1 && lanes >= 1 && lanes <= DD_PPO_FUSED_ROWS && max_steps >= 1 &&
-           lanes * (int64_t)max_steps <= DD_REINFORCE_MAX_CELLS;
-}
-
 }  // namespace rf
 }  // namespace dd
 
@@ -481,9 +353,16 @@ int dd_reinforce_train(const DDConfig* cfg, const DDState* st, const DDReinforce
     if (dd::fused::shared_between_owners(owned)) return hipErrorInvalidValue;
 
     Args a{};
-    a.k = dd::make_consts(*cfg);
-    a.obs = io->obs;
-    a.shaped_hist = shape == dd::kShapePpo ? io->shaped_hist : nullptr;
+    a.env.k = dd::make_consts(*cfg);
+    a.env.obs = io->obs;
+    a.env.shaped_hist = shape == dd::kShapePpo ? io->shaped_hist : nullptr;
+    a.env.seed = io->seed;
+    a.env.step = io->step;
+    a.env.n = n;
+    a.env.lanes = (int32_t)io->lanes_per_member;
+    a.env.frames = io->max_steps;
+    a.env.max_steps = shape == dd::kShapeNone ? 0 : io->env_max_steps;
+    a.env.shape = shape;
     a.lengths = io->lengths;
     a.ended = io->ended;
     a.episode_return = io->episode_return;
@@ -492,15 +371,8 @@ int dd_reinforce_train(const DDConfig* cfg, const DDState* st, const DDReinforce
     a.record_returns = io->record_returns;
     a.record_advantages = io->record_advantages;
     a.logs = io->logs;
-    a.seed = io->seed;
-    a.step = io->step;
-    a.n = n;
     a.member_bytes = member_bytes;
-    a.lanes = (int32_t)io->lanes_per_member;
     a.members = members;
-    a.frames = io->max_steps;
-    a.max_steps = shape == dd::kShapeNone ? 0 : io->env_max_steps;
-    a.shape = shape;
     a.normalize = io->normalize ? 1 : 0;
     const dd::Soa<float> soa = dd::soa_of<float>(*st, 0);
     const bool ref = dd::uses_reference_physics(*cfg);

@@ -34,7 +34,9 @@ and a sweep's learners updated in one fused launch (:class:`LearnerPopulation`,
 one-step actor-critic loop itself, frame by frame, in one launch
 (:func:`actor_critic_train`, :func:`actor_critic_train_population`), and
 one whole REINFORCE iteration in one launch (:class:`ReinforcePopulation`,
-:func:`reinforce_train`, :func:`reinforce_train_population`);
+:func:`reinforce_train`, :func:`reinforce_train_population`), and one whole
+PPO iteration in one launch (:func:`ppo_train`, :func:`ppo_train_population`,
+:func:`ppo_iteration_data`);
 and the frames of ``DroneGame.render`` (:meth:`VecDroneEnv.render`) and the
 labelled grid of ``--render-all`` (:meth:`VecDroneEnv.render_grid`,
 :func:`grid_shape`).
@@ -57,6 +59,7 @@ from .reward_parts import notebook_rewards
 from .population import LearnerPopulation, ReinforcePopulation, collect_ppo_population, ppo_update_population
 from .actor_critic import AC_LOG_KEYS, ActorCriticRun, actor_critic_train, actor_critic_train_population
 from .reinforce import REINFORCE_LOG_KEYS, ReinforceRun, reinforce_train, reinforce_train_population
+from .ppo_train import PPO_BATCH_LOG_KEYS, PpoRun, ppo_iteration_data, ppo_train, ppo_train_population
 
 __all__ = [
     "EnvConfig", "VecDroneEnv", "StepInfo", "OBS_KEYS", "grid_shape",
@@ -73,5 +76,6 @@ __all__ = [
     "LearnerPopulation", "ppo_update_population", "collect_ppo_population",
     "ActorCriticRun", "actor_critic_train", "actor_critic_train_population", "AC_LOG_KEYS",
     "ReinforcePopulation", "ReinforceRun", "reinforce_train", "reinforce_train_population", "REINFORCE_LOG_KEYS",
+    "PpoRun", "ppo_train", "ppo_train_population", "ppo_iteration_data", "PPO_BATCH_LOG_KEYS",
 ]
 __version__ = "0.1.0"

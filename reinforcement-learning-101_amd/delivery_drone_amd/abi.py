@@ -30,7 +30,8 @@ __all__ = [
     "DDShuffleIO", "DD_PPO_FUSED_ROWS", "DD_PPO_POLICY_GRAD_NORM", "DD_PPO_CRITIC_GRAD_NORM", "DD_PPO_FUSED_LOGS",
     "DDPpoFusedNet", "DDPpoFusedIO", "DDPpoPopulationMember", "DDPpoPopulationIO", "DDActorCriticMember",
     "DDActorCriticIO", "DD_AC_LOGS", "AC_LOG_NAMES", "DDReinforceMember", "DDReinforceIO", "DD_RF_LOGS",
-    "RF_LOG_NAMES", "DD_REINFORCE_CELL_BYTES", "DD_REINFORCE_MAX_CELLS", "DD_REWARD_PARTS", "DDRewardParts", "REWARD_PART_NAMES",
+    "RF_LOG_NAMES", "DD_REINFORCE_CELL_BYTES", "DD_REINFORCE_MAX_CELLS", "DDPpoTrainMember", "DDPpoTrainIO",
+    "DD_PPO_TRAIN_CELL_BYTES", "DD_PT_BATCH_LOGS", "PT_BATCH_LOG_NAMES", "DD_REWARD_PARTS", "DDRewardParts", "REWARD_PART_NAMES",
     "sampling_mode", "lib", "load", "library_path", "check",
     "NativeLibraryError",
 ]
@@ -74,6 +75,10 @@ RF_LOG_NAMES = ("loss", "grad_norm", "baseline", "std", "rows")
 DD_RF_LOGS = len(RF_LOG_NAMES)
 DD_REINFORCE_CELL_BYTES = 108
 DD_REINFORCE_MAX_CELLS = 1 << 24
+#: the rows of ``dd_ppo_train``'s batch logs, in the header's DD_PT_* order
+PT_BATCH_LOG_NAMES = ("rows", "adv_mean", "adv_std")
+DD_PT_BATCH_LOGS = len(PT_BATCH_LOG_NAMES)
+DD_PPO_TRAIN_CELL_BYTES = 124
 DD_TD_CRITIC_LOSS, DD_TD_MSE, DD_TD_VALUE_REG, DD_TD_COUNT, DD_TD_RESULTS = range(5)
 
 _D = ctypes.c_double
@@ -331,6 +336,26 @@ class DDReinforceIO(ctypes.Structure):
                 ("record_advantages", ctypes.c_void_p), ("logs", ctypes.c_void_p)]
 
 
+class DDPpoTrainMember(ctypes.Structure):
+    """One learner of ``dd_ppo_train``: its two networks and its coefficients."""
+
+    _fields_ = [("actor", DDPpoFusedNet), ("critic", DDPpoFusedNet), ("gamma", _D), ("lambda_", _D),
+                ("clip_epsilon", _D), ("entropy_coef", _D), ("value_coef", _D), ("max_grad_norm", _D),
+                ("shuffle_seed", ctypes.c_uint64)]
+
+
+class DDPpoTrainIO(ctypes.Structure):
+    _fields_ = [("table", ctypes.POINTER(DDPpoTrainMember)), ("members", _I), ("max_steps", _I),
+                ("lanes_per_member", ctypes.c_int64), ("obs", ctypes.c_void_p), ("shaped_hist", ctypes.c_void_p),
+                ("shaped_mode", _I), ("env_max_steps", _I), ("normalize", _I), ("num_epochs", _I),
+                ("minibatch_size", _I), ("drop_last", _I), ("shuffle_epoch", ctypes.c_uint64),
+                ("seed", ctypes.c_uint64), ("step", ctypes.c_int64), ("lengths", ctypes.c_void_p),
+                ("ended", ctypes.c_void_p), ("episode_return", ctypes.c_void_p), ("landed", ctypes.c_void_p),
+                ("record_reward", ctypes.c_void_p), ("record_done", ctypes.c_void_p),
+                ("record_values", ctypes.c_void_p), ("record_returns", ctypes.c_void_p),
+                ("record_advantages", ctypes.c_void_p), ("logs", ctypes.c_void_p), ("batch_logs", ctypes.c_void_p)]
+
+
 def sampling_mode(temperature) -> int:
     """The ``DD_SAMPLE_*`` mode of a notebook ``temperature``: 1 is the plain
     Bernoulli draw, 0 greedy (``probs > 0.5``), any other positive finite value
@@ -456,6 +481,9 @@ EXPORTS = {
     "dd_reinforce_train": (ctypes.c_int, [ctypes.POINTER(DDConfig), ctypes.POINTER(DDState),
                                           ctypes.POINTER(DDReinforceIO), ctypes.c_int64, ctypes.c_void_p,
                                           ctypes.c_void_p]),
+    "dd_ppo_train_workspace": (ctypes.c_int64, [_I, ctypes.c_int64, _I]),
+    "dd_ppo_train": (ctypes.c_int, [ctypes.POINTER(DDConfig), ctypes.POINTER(DDState), ctypes.POINTER(DDPpoTrainIO),
+                                    ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p]),
 }
 
 #: symbols a timing-only lab build (tools/build_variants.sh) or an older
@@ -471,7 +499,8 @@ _LAB_OPTIONAL = ("dd_build_info", "dd_selftest_sqrt", "dd_rollout_kernel", "dd_s
                  "dd_policy_evaluate_parts", "dd_policy_rollout_population", "dd_render_grid",
                  "dd_ppo_update_fused_workspace", "dd_ppo_update_fused", "dd_ppo_update_population_workspace",
                  "dd_ppo_update_population", "dd_actor_critic_train_workspace", "dd_actor_critic_train",
-                 "dd_reinforce_train_workspace", "dd_reinforce_train")
+                 "dd_reinforce_train_workspace", "dd_reinforce_train",
+                 "dd_ppo_train_workspace", "dd_ppo_train")
 
 
 class NativeLibraryError(RuntimeError):

@@ -102,7 +102,10 @@ class LearnerPopulation(_Population):
     population owns the update's workspace (the descriptor table, and per
     workgroup the backward's weight images, the head gradient and the row
     stage), allocated here once and sized for
-    :func:`actor_critic_train_population`'s launch as well."""
+    :func:`actor_critic_train_population`'s launch as well.
+    :func:`ppo_train_population`'s workspace depends on the lanes per member
+    and the frames of a call: it is allocated at the first such call and grown
+    when a later one needs more."""
 
     def __init__(self, members):
         super().__init__(members)
@@ -110,6 +113,13 @@ class LearnerPopulation(_Population):
         size = max(int(self._lib.dd_ppo_update_population_workspace(len(self))),
                    int(self._lib.dd_actor_critic_train_workspace(len(self))))
         self._workspace = torch.empty(size // 8, dtype=torch.int64, device=self.device)
+        self._train_workspace = None  # ppo_train_population's: allocated at the first call, grown on demand
+
+    def _train_workspace_for(self, lanes: int, max_steps: int) -> torch.Tensor:
+        size = int(self._lib.dd_ppo_train_workspace(len(self), lanes, max_steps))
+        if self._train_workspace is None or self._train_workspace.numel() * 8 < size:
+            self._train_workspace = torch.empty((size + 7) // 8, dtype=torch.int64, device=self.device)
+        return self._train_workspace
 
     @staticmethod
     def _member_nets(p, member):
